@@ -15,9 +15,12 @@ T = 2000 sqrt schedule), synthetic ComMU-shaped generation batch, torch-default 
 own batch of 64 (weak scaling; the reference shards whole batches over ranks, run/sample.py:169);
 rank 0 builds the weights and ONE RCCL broadcast of the packed arena distributes them.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus `roofline` (the kernel with the largest time share - the
-bf16 MFMA GEMM with the LayerNorm epilogue - timed live with HIP events on the launch streams) and, at N = 1,
-`cpu_baseline` (the oracle = a torch-CPU fp32 port of the reference path, timed on the host cores on a bounded sample).
+Prints ONE JSON line (rank 0) with the driver's contract: a plain run sets up, warms up, times exactly --steps steps and reports
+them (`value`, `ms_per_step`).  `--full` adds what is measured beside the headline: `roofline` (the kernel with the largest time
+share - the bf16 MFMA GEMM with the LayerNorm epilogue - timed live with HIP events on the launch streams), `kernels`, the repeated
+timed regions of `config.repeats`, and at N = 1 `cpu_baseline` (the oracle = a torch-CPU fp32 port of the reference path, timed on
+the host cores on a bounded sample) and `secondary` / `parity_mode` (training step, other precisions and widths, token agreement).
+`--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -49,6 +52,26 @@ WORKLOADS = {
 }
 MFMA_PEAK_TFLOPS = {"bf16": 2500.0, "fp32": 157.3}   # dense peaks, MI355X_MICROARCH.md
 HBM_PEAK_GBS = 8000.0                                 # HBM3E spec (6.3 TB/s achievable with a float4 copy, same guide)
+DUMP_BYTES = 60 * 10**6                               # --dump-outputs: array data over all files (64 MB with room for the headers)
+
+
+def dump_outputs(dirname, arrays):
+    """`--dump-outputs DIR`: the arrays {name: tensor} a caller of the timed path receives from its last step, as DIR/<name>.npy.
+    Floating point is written as float32 (float64 stays float64), integers (tokens) as float64, which holds them exactly.  Should the
+    arrays exceed DUMP_BYTES together, each keeps the same fraction of its elements: a fixed sample (seed 0, sorted flat indices)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.double() if (t.dtype == torch.float64 or not t.is_floating_point()) else t.float()
+        host[name] = t.cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    for name, a in host.items():
+        if total > DUMP_BYTES:
+            keep = max(1, int(a.size * DUMP_BYTES // total))
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def step_flops(c):
@@ -518,10 +541,12 @@ def train_main(args, world, rank, local_rank, device):
         return losses, gn
     elapsed, (losses, gn) = timed_region(timed, world, device)
     assert bool(torch.isfinite(losses["loss"])) and bool(torch.isfinite(gn).all())
-    # the gradient all-reduce's EXPOSED time: the same steps with DDP's all-reduce suppressed on every micro-batch (no_sync) - the
-    # difference is what the collective adds to a step after its overlap with the backward (0 by construction at N = 1)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict({"losses_" + k: v for k, v in losses.items()}, grad_norm=gn))
+    # the gradient all-reduce's EXPOSED time (--full): the same steps with DDP's all-reduce suppressed on every micro-batch (no_sync) -
+    # the difference is what the collective adds to a step after its overlap with the backward (0 by construction at N = 1)
     nosync_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         def timed_nosync():
             for _ in range(args.steps):
                 with ddp.no_sync():
@@ -715,6 +740,8 @@ def sampling_main(args, world, rank, local_rank, device):
         run(min(args.warmup, steps))
     elapsed, tokens = timed_region(lambda: run(steps), world, device)
     assert tokens.shape == (Bg, c["L"]) and tokens.dtype == torch.int64
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"tokens": tokens})
     assert_same_on_all_ranks(int(tokens.sum().item()) * 1000003 + int((tokens * torch.arange(1, c["L"] + 1, device=tokens.device)).sum().item()),
                              "gathered token checksum", world, device)
     if rank == 0:
@@ -859,7 +886,7 @@ def secondary_block(device, budget_note="short timed regions: <= 60 s in total")
     return sec
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default 200: 0.8 s of replay; train: 10; c3: fixed by the config)")
@@ -871,8 +898,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--sampler", default="uniform", choices=["uniform", "lossaware"], help="train: the timestep sampler (lossaware = the reference's default)")
-    ap.add_argument("--repeats", type=int, default=4, help="sampling workloads: further back-to-back repetitions of the timed region, reported in config.repeats (value = the median region)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the `secondary` object (train / fp32 / bertbase / token agreement) of the default N = 1 config-2 line")
+    ap.add_argument("--full", action="store_true", help="also what is measured beside the headline: roofline + kernels, cpu_baseline, secondary + parity_mode "
+                                                        "(N = 1 config 2), repeated timed regions, the all-reduce's exposed time (train, N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--repeats", type=int, default=None, help="sampling workloads: further back-to-back repetitions of the timed region, reported in config.repeats (value = the median region; default 4 with --full, else 0)")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the `secondary` object (train / fp32 / bertbase / token agreement) of the N = 1 config-2 line")
     ap.add_argument("--accum", type=int, default=1, help="train: micro-batches per optimizer step (the reference's batch_size // microbatch)")
     ap.add_argument("--split", type=int, default=None, help="batch slices run as concurrent graph branches (default: the library's choice)")
     ap.add_argument("--gemm", type=int, default=None, help="bf16 GEMM kernel variant 0 / 2 / 4 (see mh_gemm_set_variant)")
@@ -882,10 +912,18 @@ def main():
     ap.add_argument("--no-decouple", action="store_true", help="A/B: one graph per step with a fork / join of the batch slices instead of one free-running graph per slice (the default where the fused step boundary runs)")
     ap.add_argument("--decouple", action="store_true", help="A/B: force the free-running graphs (widths without the fused boundary default to the fork / join)")
     ap.add_argument("--skew-us", type=int, default=None, help="phase lag between the decoupled batch-slice chains in microseconds (default: half a step)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps is None:
         args.steps = {"train": 10}.get(args.workload, 200)
+    if not args.full:      # a plain run does what its headline needs and nothing else
+        args.no_cpu_baseline = args.no_kernel_timing = args.no_secondary = True
+    if args.repeats is None:
+        args.repeats = 4 if args.full else 0
+    return args
 
+
+def main():
+    args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus, sys.argv[1:])          # does not return
     world, rank, local_rank, device = init_ranks(args)
@@ -960,6 +998,9 @@ def main():
     all_tokens = sharding.gather_rows(tokens, c["B"] * world)      # one token all-gather (run/sample.py:288-291)
     assert all_tokens.shape == (c["B"] * world, c["L"])
     assert_same_on_all_ranks(int(all_tokens.sum().item()), "gathered token checksum", world, device)
+    if args.dump_outputs and rank == 0:
+        # what the loop hands its caller (_ReverseLoop.run: sample, pred_xstart of this rank's batch) and the tokens made of it
+        dump_outputs(args.dump_outputs, {"sample": loop.x, "pred_xstart": loop.pred, "tokens": all_tokens})
 
     if rank == 0:
         first_ms = elapsed / args.steps * 1e3

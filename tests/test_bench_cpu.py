@@ -1,5 +1,6 @@
 """bench.py's launcher logic (no GPU): `--gpus N` without a launcher starts N ranks through torch.distributed.run as a child
-process; a WORLD_SIZE that disagrees with --gpus is an error, also when it is 1."""
+process; a WORLD_SIZE that disagrees with --gpus is an error, also when it is 1.  Also what a plain run leaves to --full, and the
+files of --dump-outputs."""
 import os
 import subprocess
 import sys
@@ -49,3 +50,37 @@ def test_main_self_launches_when_no_launcher(monkeypatch):
     with pytest.raises(SystemExit):
         bench.main()
     assert called == {"n": 2, "argv": ["--gpus", "2", "--steps", "1"]}
+
+
+def test_plain_run_times_the_headline_only():
+    """A plain `--gpus 1 --steps N --warmup W` run times exactly N steps and measures nothing beside them; --full brings back the
+    roofline / kernel tables, the CPU baseline, the secondary block and the repeated regions, each of which can still be switched off."""
+    sys.path.insert(0, REPO)
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.repeats, a.full, a.dump_outputs) == (7, 2, 0, False, None)
+    assert a.no_cpu_baseline and a.no_kernel_timing and a.no_secondary
+    f = bench.parse_args(["--steps", "7", "--full"])
+    assert f.repeats == 4 and not (f.no_cpu_baseline or f.no_kernel_timing or f.no_secondary)
+    f = bench.parse_args(["--full", "--no-secondary", "--repeats", "2"])
+    assert f.repeats == 2 and f.no_secondary and not f.no_cpu_baseline
+
+
+def test_dump_outputs_types_and_budget(tmp_path, monkeypatch):
+    """--dump-outputs: float32 for floating tensors (float64 kept), float64 for integers; above the byte budget a fixed sample of each."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    x = torch.randn(4, 8, dtype=torch.bfloat16)
+    tok = torch.arange(32, dtype=torch.int64).reshape(4, 8)
+    bench.dump_outputs(str(tmp_path / "a"), {"x": x, "d": torch.ones(3, dtype=torch.float64), "tokens": tok})
+    got = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in ("x", "d", "tokens")}
+    assert got["x"].dtype == np.float32 and np.array_equal(got["x"], x.float().numpy())
+    assert got["d"].dtype == np.float64 and got["tokens"].dtype == np.float64 and np.array_equal(got["tokens"], tok.numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1000)
+    big = torch.randn(1000)
+    for sub in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / sub), {"big": big})
+    b, c = np.load(str(tmp_path / "b" / "big.npy")), np.load(str(tmp_path / "c" / "big.npy"))
+    assert b.nbytes <= 1000 and b.size == 250 and np.array_equal(b, c) and np.isin(b, big.numpy()).all()

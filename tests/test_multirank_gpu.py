@@ -66,7 +66,7 @@ def test_bench_gpus_2_self_launches_and_reports_two_ranks(workload):
     if torch.cuda.device_count() < 2:
         env["MUSE_BENCH_SHARE_GPU"] = "1"
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--workload", workload, "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline", "--no-kernel-timing"]
+           "--full", "--no-cpu-baseline", "--no-kernel-timing"]      # --full: the training line's all-reduce exposed time
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-3000:])
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

@@ -1,9 +1,8 @@
 """The recipe of INTEGRATION.md section 1, executed: tests/shim/MuseDiffusion/ holds exactly the re-export modules a maintainer would
-write, and the hot path is imported THROUGH those names.  CPU part: the import surface and - where the reference
-checkout exists (the build container) - the reference's REAL utils/initialization.py running over the shim: its import site
-(utils/initialization.py:110-112) then binds to this package's classes."""
+write, and the hot path is imported THROUGH those names.  CPU part: the import surface and the factory module of the
+shim, which issues the reference's import site (utils/initialization.py:110-112) through the same names: it binds to this package's
+classes."""
 import importlib
-import importlib.util
 import os
 import sys
 from types import SimpleNamespace
@@ -11,7 +10,6 @@ from types import SimpleNamespace
 import pytest
 
 SHIM = os.path.join(os.path.dirname(os.path.abspath(__file__)), "shim")
-REF_INIT = "/root/reference/MuseDiffusion/utils/initialization.py"
 
 
 @pytest.fixture()
@@ -54,17 +52,15 @@ def test_import_surface_through_the_reference_names(shim_path):
     assert importlib.import_module("MuseDiffusion.models.nn").timestep_embedding is ours_n.TransformerNetModel.timestep_embedding
 
 
-@pytest.mark.skipif(not os.path.exists(REF_INIT), reason="the reference checkout exists in the build container only")
-def test_the_reference_factory_file_runs_over_the_shim(shim_path):
-    """The reference's own create_model_and_diffusion (loaded from its file, unmodified) builds THIS package's classes when the four
-    model modules are the re-exports: same constructor keywords, same defaults (bert-base-uncased shape, network.py:44-46)."""
+def test_the_factory_stand_in_runs_over_the_shim(shim_path):
+    """create_model_and_diffusion as the reference's factory module issues it (its imports inside the function, through the
+    `MuseDiffusion.models.*` names) builds THIS package's classes when the four model modules are the re-exports: same constructor
+    keywords, same defaults (bert-base-uncased shape, network.py:44-46)."""
     import torch
     import musediffusion_amd.models.diffusion as ours_d
     import musediffusion_amd.models.network as ours_n
-    spec = importlib.util.spec_from_file_location("_reference_initialization", REF_INIT)
-    mod = importlib.util.module_from_spec(spec)
-    sys.dont_write_bytecode = True
-    spec.loader.exec_module(mod)
+    mod = importlib.import_module("MuseDiffusion.utils.initialization")
+    assert os.path.dirname(mod.__file__).startswith(SHIM)
     args = SimpleNamespace(hidden_dim=128, hidden_t_dim=128, vocab_size=729, seq_len=64, dropout=0.1, noise_schedule="sqrt",
                            diffusion_steps=2000, timestep_respacing="", rescale_timesteps=True, predict_xstart=True)
     model, diffusion = mod.create_model_and_diffusion(args)
