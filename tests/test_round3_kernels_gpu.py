@@ -14,6 +14,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import gemm_census as gc  # noqa: E402
 from musediffusion_amd import _lib, ops  # noqa: E402
 from musediffusion_amd._lib import MH_BF16, check, current_stream, lib  # noqa: E402
 
@@ -122,6 +123,12 @@ def test_gelu_derivative_stored_by_the_forward():
     exact = (dy.float() @ W2T.float().T) * dact.float()
     assert float((d1.float() - exact).abs().max()) <= 2.0 ** -8 * float(exact.abs().max()) + 1e-6
     assert float((d1.float() - d0.float()).abs().max()) <= 0.02 * float(d0.float().abs().max())
+    # the generic act-grad epilogue (gelu' evaluated from the stored pre-activation), element by element against float64: the derivative's
+    # 2e-4 (as for the stored derivative above) scaled by |dY W2|, and the bf16 rounding of the output
+    gdy = dy.double() @ W2T.double().T
+    ref0 = gdy * (0.5 * (1 + torch.erf(pre.double() / math.sqrt(2))) + pre.double() * torch.exp(-pre.double() ** 2 / 2) / math.sqrt(2 * math.pi))
+    err0 = (d0.double() - ref0).abs()
+    assert bool((err0 <= 2e-4 * gdy.abs() + 2.0 ** -8 * ref0.abs() + 1e-6).all()), "act_grad(gelu): max err %.3e" % float(err0.max())
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -130,18 +137,7 @@ def test_gelu_derivative_stored_by_the_forward():
 # re-expression of the decision code (round 3: one 16-bit compare per element instead of three byte compares) can be checked without an
 # old build of the library.
 
-def _philox7(c, k0, k1):
-    import numpy as np
-    c = [x.astype(np.uint64) for x in c]
-    k0, k1 = np.uint64(k0), np.uint64(k1)
-    M0, M1, W0, W1, MASK = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57), np.uint64(0x9E3779B9), np.uint64(0xBB67AE85), np.uint64(0xFFFFFFFF)
-    for _ in range(7):
-        p0, p1 = M0 * c[0], M1 * c[2]
-        n0 = (p1 >> np.uint64(32)) ^ c[1] ^ k0
-        n2 = (p0 >> np.uint64(32)) ^ c[3] ^ k1
-        c = [n0 & MASK, p1 & MASK, n2 & MASK, p0 & MASK]
-        k0, k1 = (k0 + W0) & MASK, (k1 + W1) & MASK
-    return c
+_philox7 = gc.philox7
 
 
 @pytest.mark.parametrize("BH,L,p", [(3, 96, 0.1), (2, 528, 0.37), (1, 64, 0.0039)])
@@ -192,14 +188,7 @@ def test_dense_site_keep_flags_follow_the_documented_rule():
     check(lib().mh_dropout_fwd(x.data_ptr(), cols, out.data_ptr(), cols, rows, cols, 0, C.byref(d), current_stream()))     # dtype 0 = fp32
     got = (out.cpu().numpy() != 0).reshape(-1)
     assert np.allclose(out.cpu().numpy()[out.cpu().numpy() != 0], 1.0 / (1.0 - p), rtol=1e-6)
-    thr = int(np.float32(p) * np.float32(65536.0) + np.float32(0.5))
-    g = np.arange(rows * cols // 8, dtype=np.uint64)
-    c = _philox7([g & np.uint64(0xFFFFFFFF), g >> np.uint64(32), np.full(g.shape, offset & 0xFFFFFFFF, np.uint64), np.full(g.shape, offset >> 32, np.uint64)],
-                 seed & 0xFFFFFFFF, seed >> 32)
-    keep = np.zeros((g.size, 8), dtype=bool)
-    for w in range(4):
-        keep[:, 2 * w] = (c[w] & np.uint64(0xFFFF)) >= np.uint64(thr)
-        keep[:, 2 * w + 1] = (c[w] >> np.uint64(16)) >= np.uint64(thr)
+    keep = gc.dense_keep(rows, cols, p, seed, offset)
     assert np.array_equal(got, keep.reshape(-1))
 
 

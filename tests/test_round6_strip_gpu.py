@@ -54,7 +54,9 @@ def test_strip_kernel_writes_the_big_tile_kernels_bits(dbg, M, N):
     assert torch.equal(outs[0], outs[1])
     ref = torch.nn.functional.gelu(X.float() @ W.float().t() + b)
     got = _rows(outs[0], M, N).float()
-    assert (got - ref).abs().max().item() <= 2e-2 + 8e-3 * ref.abs().max().item()   # bf16 output rounding
+    # bf16 output rounding, per element (a wrong tile of small values must not hide under the largest value's allowance)
+    err = (got - ref).abs()
+    assert bool((err <= 2e-2 + 8e-3 * ref.abs()).all()), "max err %.3e" % err.max().item()
 
 
 def test_strip_kernel_on_a_row_window_of_larger_panels(dbg):
@@ -80,7 +82,7 @@ def test_strip_kernel_on_a_row_window_of_larger_panels(dbg):
     assert (o[:, :R0] == 7.0).all() and (o[:, R0 + M:] == 7.0).all()
     ref = torch.nn.functional.gelu(Xall[R0:R0 + M].float() @ W.float().t() + b)
     got = o[:, R0:R0 + M].permute(1, 0, 2).reshape(M, N).float()
-    assert (got - ref).abs().max().item() <= 2e-2 + 8e-3 * ref.abs().max().item()
+    assert bool(((got - ref).abs() <= 2e-2 + 8e-3 * ref.abs()).all())
 
 
 def test_shapes_the_strip_kernel_does_not_serve_are_unchanged(dbg):
@@ -101,4 +103,4 @@ def test_shapes_the_strip_kernel_does_not_serve_are_unchanged(dbg):
         assert torch.equal(outs[0], outs[1])
         y = X.float() @ W.float().t() + b
         ref = torch.nn.functional.gelu(y) if act == 2 else y
-        assert (_rows(outs[0], M, N).float() - ref).abs().max().item() <= 2e-2 + 8e-3 * ref.abs().max().item()
+        assert bool(((_rows(outs[0], M, N).float() - ref).abs() <= 2e-2 + 8e-3 * ref.abs()).all())
