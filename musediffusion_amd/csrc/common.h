@@ -7,7 +7,10 @@
 
 // A/B switches, ablation knobs and diagnostics (include/musehip_dbg.h) exist only in the debug library (-DMH_ABLATE ->
 // libmusehip_dbg.so).  The production library has no process-global mutable configuration: there every MH_KNOB is a compile-time
-// constant holding the default, the setters are not compiled, and the kernel variants only a knob can reach are dead code.
+// constant holding the default and the setters are not compiled.  A constant-false `if` does NOT keep a kernel out of the library (the
+// launch in its body still instantiates the template), so a launch site that only a knob away from its default can reach stands inside
+// #ifdef MH_ABLATE: the product library does not contain the kernel at all.  DESIGN.md, "GEMM sources", lists what that removes and
+// how the product's kernel list is compared against the debug library's.
 // per-device bookkeeping of hipFuncSetAttribute (it acts on the CURRENT device's copy of a kernel): the library may serve several
 // devices from one process
 constexpr int MH_MAX_DEVICES = 64;

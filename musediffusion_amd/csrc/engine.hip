@@ -383,7 +383,7 @@ int denoiser_run(const mh_denoiser* m, const float* x, const float* emb_t, const
         return rc;
     }
     const int nLrun = (ph.mask & 2) ? m->nL : 0;     // (the layer loops below run only in phase 2)
-    // Deferred LayerNorm (DeferArgs, gemm.hip): the attention-output and FFN-output GEMMs store RAW rows + partial row
+    // Deferred LayerNorm (DeferArgs, gemm_args.h): the attention-output and FFN-output GEMMs store RAW rows + partial row
     // statistics and their consumers normalise on the fly, so every GEMM runs on the 256x128 tile (no full-row tile, no
     // LayerNorm kernel - d_model 768 included).  The last layer's output is normalised by the panel LayerNorm kernel.
     // Measured (same box, tools: bench.py --defer-ln 0/2): +2% steps/s at d_model 768 (two LayerNorm kernels per layer

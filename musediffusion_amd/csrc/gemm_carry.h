@@ -1,4 +1,4 @@
-// gemm_carry.h - included by gemm.hip inside its anonymous namespace; libmusehip_dbg.so (-DMH_ABLATE) only.
+// gemm_carry.h - included by gemm_strip.hip inside namespace mhgemm; libmusehip_dbg.so (-DMH_ABLATE) only.
 //
 // Round-6 experiment (round-5 verdict, item 5): FFN1's dense + bias + GELU with the PREVIOUS tile's epilogue carried under the next tile's
 // K loop.  The product kernel (gemm_big_kernel<CfgStd, 0, GELU>) runs a tile's 16 K-steps and then its 16 epilogue groups, two blocks per CU:

@@ -1,4 +1,4 @@
-// gemm_strip.h - included by gemm.hip inside its anonymous namespace (both builds).
+// gemm_strip.h - included by gemm_strip.hip inside namespace mhgemm (both builds).
 //
 // Round 6: dense + bias + GELU of K32-panel operands into a K32-panel bf16 output - the sampler's FFN1 - as a "column strip" kernel.  It came
 // out of the carried-epilogue experiment (gemm_carry.h, profiles/r06_ffn1_carry.txt): carrying a tile's epilogue under the next tile's K loop

@@ -8,7 +8,7 @@
 // first dense layer stays in LDS as the second one's A operand, only the weights stream (L2 -> LDS by LDS-DMA, 3-stage ring of
 // whole K32 steps: H rows x 64 B), and the LayerNorm runs on the fp32 accumulators.
 //
-// Layouts are gemm.hip's: LDS rows of 64 B (one K32 step), 16-byte chunk c of row r at c ^ G[(r >> 2) & 3], G = {0, 2, 3, 1}
+// Layouts are gemm_big.h's: LDS rows of 64 B (one K32 step), 16-byte chunk c of row r at c ^ G[(r >> 2) & 3], G = {0, 2, 3, 1}
 // (conflict-free ds_read_b128 fragments); DMA pieces of 16 rows x 64 B with the swizzle on the SOURCE address; MFMA 16x16x32 bf16
 // issued as D = W_tile . A_tile^T with the W rows of a wave's 64 columns dealt to the MFMA input rows as
 // 32 (jj >> 1) + 8 (p >> 2) + 4 (jj & 1) + (p & 3), so that a lane owns 8 CONSECUTIVE output columns of one row.

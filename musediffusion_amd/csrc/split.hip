@@ -191,7 +191,7 @@ __global__ __launch_bounds__(256) void split_ln_kernel(const float* __restrict__
 // ------------------------------------------------------------------------------------------ GEMM
 // out = act(A W^T + bias) [+ residual]: A split panels [2][K/32][lda][32] (M rows), W split panels [2][K/32][ldw][32] (N rows).
 // 256 x 128 tile, 4 waves (2 x 2, 128 x 64 each), 3-stage LDS-DMA ring of K-steps of 32, two blocks per CU: the bf16 path's
-// geometry (csrc/gemm.hip, BigCfg<256,128,2,2,3>), LDS rows of 64 B with the chunk swizzle c ^ G[(r >> 2) & 3], the W-row remap that
+// geometry (csrc/gemm_args.h, BigCfg<256,128,2,2,3>), LDS rows of 64 B with the chunk swizzle c ^ G[(r >> 2) & 3], the W-row remap that
 // leaves a lane 8 consecutive output columns.
 struct SpGemmArgs {
   const void* A; int64_t lda;
@@ -231,7 +231,7 @@ __global__ __launch_bounds__(256, 2) void split_gemm_kernel(const SpGemmArgs g) 
   constexpr int GSW[4] = {0, 2, 3, 1};
   // DMA coordinates: a piece = 16 rows x 64 B; lane i lands at row i / 4, physical chunk i % 4, which holds logical chunk pc ^ G[..]
   const int rl = lane >> 2, pc = lane & 3, lc = pc ^ GSW[(rl >> 2) & 3];
-  // The stage DMA as `buffer_load_dwordx4 ... lds` (round 5, as csrc/gemm.hip BufDma): the tile's rows of part 0, panel 0 as the base of a buffer
+  // The stage DMA as `buffer_load_dwordx4 ... lds` (round 5, as csrc/gemm_big.h BufDma): the tile's rows of part 0, panel 0 as the base of a buffer
   // descriptor (scalar registers), the (part, panel) of the stage as the instruction's scalar offset, a wave's consecutive pieces as its
   // immediate offset (which advances the LDS address with the buffer address) and ONE per-lane offset: no vector address arithmetic per piece.
   // Rows beyond M / N are not clamped: inside the buffer they read other rows (never stored); the descriptor ends with the rows this operand OWNS in
@@ -411,7 +411,7 @@ __global__ __launch_bounds__(256, 2) void split_gemm_kernel(const SpGemmArgs g) 
 // ---- dense + residual + LayerNorm in one kernel (hidden size 512): out = LN(A W^T + bias + residual) as split panels.
 // A block owns 128 COMPLETE rows (128 x 512 tile, 8 waves as 2 x 4, 64 x 128 each, 3 stages of 40 KB, one block per CU - the bf16 path's
 // full-row tile); stages per K-step: {A hi, W lo} then {A lo, W hi}, the hi x hi product on the A hi fragments kept from the first.
-// Epilogue as csrc/gemm.hip EPI 3: two-pass statistics, in-lane -> the 4 lanes of a row -> the 4 column waves through LDS.
+// Epilogue as csrc/gemm_big.h EPI 3: two-pass statistics, in-lane -> the 4 lanes of a row -> the 4 column waves through LDS.
 constexpr int RBM = 128, RBN = 512, RNST = 3, RSTAGE = (RBM + RBN) * 64, RTI = 4, RTJ = 8, RPW = 4, RPIECES = 1 + RPW;
 __device__ __forceinline__ void sp_wait_stages_r(int stages) {
   if (stages >= 2) sp_wait_vmcnt<2 * RPIECES>();

@@ -80,7 +80,7 @@ class DenoiserEngine:
             mat(p + "w_ff1", F, H); vec(p + "b_ff1", F)
             mat(p + "w_ff2", H, F); vec(p + "b_ff2", H)
             vec(p + "ln2_g", H); vec(p + "ln2_b", H)
-            if c["fold_ln"]:   # deferred LayerNorm (csrc/gemm.hip DeferArgs): weights folded with the gain of the LayerNorm feeding them
+            if c["fold_ln"]:   # deferred LayerNorm (csrc/gemm_args.h DeferArgs): weights folded with the gain of the LayerNorm feeding them
                 if l > 0:
                     mat(p + "w_qkv_f", 3 * H, H); vec(p + "c1_qkv", 3 * H); vec(p + "c2_qkv", 3 * H)
                 mat(p + "w_ff1_f", F, H); vec(p + "c1_ff1", F); vec(p + "c2_ff1", F)

@@ -1,4 +1,4 @@
-"""Deferred LayerNorm (csrc/gemm.hip DeferArgs; HF BertSelfOutput / BertOutput LayerNorms reached from MuseDiffusion/models/
+"""Deferred LayerNorm (csrc/gemm_args.h DeferArgs; HF BertSelfOutput / BertOutput LayerNorms reached from MuseDiffusion/models/
 network.py:151): the attention-output / FFN-output GEMMs store raw rows + partial row statistics and their consumers normalise on
 the fly.  The three forward modes of the bf16 engine (0 = LayerNorm epilogues / kernels, 1 = default, 2 = deferred everywhere) must
 agree with each other within bf16 rounding and each with the fp32 oracle within the stated bf16 tolerance
