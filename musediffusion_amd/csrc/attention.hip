@@ -1111,6 +1111,7 @@ int launch_f32(const float* q, const float* k, const float* vt, float* ctx, int6
     attr_set[dev] = true;
   }
   dim3 grid(ceil_div(L, 64), B * nh), block(256);
+  mh_prof_note("attn_small kind=f32 B*nh=%d L=%d dh=%d", B * nh, L, DH);
   MH_LAUNCH((attn_f32_kernel<DH>), grid, block, bytes, s, q, k, vt, ctx, ld, L, nh, scale);
   MH_CHECK_LAUNCH();
   return MH_OK;
@@ -1131,6 +1132,7 @@ int launch_bf16(const bf16* q, const bf16* k, const bf16* vt, bf16* ctx, int64_t
       attr_set[dev] = true;
     }
     // 16 waves (four per SIMD) when the sequence has a 32-query tile for each of them
+    mh_prof_note("attn_small kind=%s B*nh=%d L=%d dh=%d", g_attn_resident == 2 && L >= 512 ? "res16" : "res8", B * nh, L, DH);
     if (g_attn_resident == 2 && L >= 512)
       MH_LAUNCH((attn_res_bf16_kernel<DH, 16>), dim3(B * nh), dim3(1024), res_bytes, s, q, k, vt, ctx, ld, L, nh,
                 scale * 1.4426950408889634f, ctx_panel, g_attn_prof);
@@ -1141,6 +1143,7 @@ int launch_bf16(const bf16* q, const bf16* k, const bf16* vt, bf16* ctx, int64_t
     return MH_OK;
   }
   dim3 grid(ceil_div(L, 128), B * nh), block(256);
+  mh_prof_note("attn_small kind=tiled B*nh=%d L=%d dh=%d", B * nh, L, DH);
   MH_LAUNCH((attn_bf16_kernel<DH>), grid, block, 0, s, q, k, vt, ctx, ld, L, nh,
                      scale * 1.4426950408889634f, ctx_panel);
   MH_CHECK_LAUNCH();
@@ -1209,6 +1212,14 @@ extern "C" int mh_attention_stream_fwd_prescaled(const void* q, const void* k, c
                          nullptr, 0, true, stream);
 }
 namespace {
+// which instantiation a launch is, for the launch note (every instantiation has the same function type, so the pointer cannot tell):
+// of<...>() takes the kernel's template arguments with the kernel's defaults
+struct StreamVariant {
+  int nw, sk, dropv, full, kvnt, pre;
+  template <int DH, int NW = 16, int SK = 256, int DROP = 0, bool FULL = false, bool KVNT = false, bool PRE = false, int ABL = 0, int PRIO = 0>
+  static constexpr StreamVariant of() { return {NW, SK, DROP, FULL, KVNT, PRE}; }
+};
+#define MH_STREAM_GO(bytes, ...) go(&attn_stream_bf16_kernel<__VA_ARGS__>, bytes, StreamVariant::of<__VA_ARGS__>())
 int stream_fwd_impl(const void* q, const void* k, const void* vt_perm, void* ctx, int64_t ld_ctx, int ctx_panel, int B, int L, int nh, int dh,
                     float scale, float* lse2, int64_t qsB, int64_t qsH, int64_t qld, const mh_dropout* drop, uint32_t* keep_bits, int bits_in,
                     bool pre, mh_stream_t stream) {
@@ -1240,7 +1251,7 @@ int stream_fwd_impl(const void* q, const void* k, const void* vt_perm, void* ctx
   const int qper = small ? 256 : 512, nitems = nbh * ((L + qper - 1) / qper);
   const int slots = g_attn_stream == 5 ? cus : (g_attn_stream == 6 ? cus / 2 : (small ? 2 * cus : cus));
   const dim3 grid((unsigned)(nitems < slots ? nitems : slots)), block(small ? 512 : 1024);
-  auto go = [&](auto kern, int bytes) -> int {
+  auto go = [&](auto kern, int bytes, StreamVariant v) -> int {
     // all instantiations share one function-pointer type, so this lambda body exists once: the attribute is tracked per kernel
     static std::set<std::pair<int, const void*>> attr_done;   // (device, kernel); guarded: the library may be called from several host threads
     static std::mutex attr_mu;
@@ -1249,7 +1260,8 @@ int stream_fwd_impl(const void* q, const void* k, const void* vt_perm, void* ctx
       if (attr_done.insert({mh_current_device(), reinterpret_cast<const void*>(kern)}).second)
         MH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
     }
-    mh_prof_note("attn_stream B*nh=%d L=%d dh=%d drop=%d", nbh, L, dh, (int)dropping);
+    mh_prof_note("attn_stream B*nh=%d L=%d dh=%d drop=%d nw=%d sk=%d dropv=%d full=%d kvnt=%d pre=%d items=%d", nbh, L, dh, (int)dropping, v.nw, v.sk,
+                 v.dropv, v.full, v.kvnt, v.pre, nitems);
     MH_LAUNCH(kern, grid, block, bytes, s, Q, K, V, (bf16*)ctx, ld_ctx, L, nh, nbh, sl2, ctx_panel, lse2, qsB, qsH, qld, da, keep_bits, bits_in);
     return MH_OK;
   };
@@ -1274,35 +1286,35 @@ int stream_fwd_impl(const void* q, const void* k, const void* vt_perm, void* ctx
   int rc;
   const bool full = L % 256 == 0 && g_attn_stream != 4;   // (mode 4 = A/B: the key-bound build on every length)
   if (dropping && bits_in && small) {   // (mode 2: the bit reader on the 8-wave geometry too)
-    rc = dh == 64 ? go(&attn_stream_bf16_kernel<64, 8, 128, 2>, 4 * 128 * 64 * 2) : go(&attn_stream_bf16_kernel<32, 8, 256, 2>, 4 * 256 * 32 * 2);
+    rc = dh == 64 ? MH_STREAM_GO(4 * 128 * 64 * 2, 64, 8, 128, 2) : MH_STREAM_GO(4 * 256 * 32 * 2, 32, 8, 256, 2);
   } else if (dropping && bits_in && full && dh == 64) {   // (round 6: the reader without the per-score bound compares where no tile is partial - config 5's seq_len 1024)
-    rc = go(&attn_stream_bf16_kernel<64, 16, 256, 2, true>, 4 * 256 * 64 * 2);
+    rc = MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 2, true);
   } else if (dropping && bits_in) {
-    rc = dh == 64 ? go(&attn_stream_bf16_kernel<64, 16, 256, 2>, 4 * 256 * 64 * 2) : go(&attn_stream_bf16_kernel<32, 16, 256, 2>, 4 * 256 * 32 * 2);
-  } else if (dropping && !small) rc = dh == 64 ? go(&attn_stream_bf16_kernel<64, 16, 256, 1>, 4 * 256 * 64 * 2) : go(&attn_stream_bf16_kernel<32, 16, 256, 1>, 4 * 256 * 32 * 2);
-  else if (dropping) rc = dh == 64 ? go(&attn_stream_bf16_kernel<64, 8, 128, 1>, 4 * 128 * 64 * 2) : go(&attn_stream_bf16_kernel<32, 8, 256, 1>, 4 * 256 * 32 * 2);
+    rc = dh == 64 ? MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 2) : MH_STREAM_GO(4 * 256 * 32 * 2, 32, 16, 256, 2);
+  } else if (dropping && !small) rc = dh == 64 ? MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 1) : MH_STREAM_GO(4 * 256 * 32 * 2, 32, 16, 256, 1);
+  else if (dropping) rc = dh == 64 ? MH_STREAM_GO(4 * 128 * 64 * 2, 64, 8, 128, 1) : MH_STREAM_GO(4 * 256 * 32 * 2, 32, 8, 256, 1);
   else if (pre) {
     // pre-scaled queries (the sampler's forward): 16 waves, the same FULL / KVNT choices as below
     MH_CHECK_ARG(mh_attention_stream_prescaled_supported(L, dh), "attention_stream(pre-scaled): seq_len %d must be a multiple of 256", L);
-    if (L <= 512) rc = dh == 64 ? go(&attn_stream_bf16_kernel<64, 16, 256, 0, true, true, true>, 4 * 256 * 64 * 2) : go(&attn_stream_bf16_kernel<32, 16, 256, 0, true, true, true>, 4 * 256 * 32 * 2);
-    else rc = dh == 64 ? go(&attn_stream_bf16_kernel<64, 16, 256, 0, true, false, true>, 4 * 256 * 64 * 2) : go(&attn_stream_bf16_kernel<32, 16, 256, 0, true, false, true>, 4 * 256 * 32 * 2);
+    if (L <= 512) rc = dh == 64 ? MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, true) : MH_STREAM_GO(4 * 256 * 32 * 2, 32, 16, 256, 0, true, true, true);
+    else rc = dh == 64 ? MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, false, true) : MH_STREAM_GO(4 * 256 * 32 * 2, 32, 16, 256, 0, true, false, true);
   }
   else if (g_attn_abl && full && !small && L <= qper && dh == 64) {
     switch (g_attn_abl) {
-      case 1: rc = go(&attn_stream_bf16_kernel<64, 16, 256, 0, true, true, false, 1>, 4 * 256 * 64 * 2); break;
-      case 2: rc = go(&attn_stream_bf16_kernel<64, 16, 256, 0, true, true, false, 2>, 4 * 256 * 64 * 2); break;
-      case 4: rc = go(&attn_stream_bf16_kernel<64, 16, 256, 0, true, true, false, 4>, 4 * 256 * 64 * 2); break;
-      case 6: rc = go(&attn_stream_bf16_kernel<64, 16, 256, 0, true, true, false, 6>, 4 * 256 * 64 * 2); break;
-      case 7: rc = go(&attn_stream_bf16_kernel<64, 16, 256, 0, true, true, false, 7>, 4 * 256 * 64 * 2); break;
-      case 8: rc = go(&attn_stream_bf16_kernel<64, 16, 256, 0, true, true, false, 8>, 4 * 256 * 64 * 2); break;
-      case 16: rc = go(&attn_stream_bf16_kernel<64, 16, 256, 0, true, true, false, 16>, 4 * 256 * 64 * 2); break;
-      case 24: rc = go(&attn_stream_bf16_kernel<64, 16, 256, 0, true, true, false, 24>, 4 * 256 * 64 * 2); break;
-      case 31: rc = go(&attn_stream_bf16_kernel<64, 16, 256, 0, true, true, false, 31>, 4 * 256 * 64 * 2); break;
-      case 63: rc = go(&attn_stream_bf16_kernel<64, 16, 256, 0, true, true, false, 63>, 4 * 256 * 64 * 2); break;
-      case 95: rc = go(&attn_stream_bf16_kernel<64, 16, 256, 0, true, true, false, 95>, 4 * 256 * 64 * 2); break;
-      case 127: rc = go(&attn_stream_bf16_kernel<64, 16, 256, 0, true, true, false, 127>, 4 * 256 * 64 * 2); break;
-      case 32: rc = go(&attn_stream_bf16_kernel<64, 16, 256, 0, true, true, false, 32>, 4 * 256 * 64 * 2); break;
-      case 128: rc = go(&attn_stream_bf16_kernel<64, 16, 256, 0, true, true, false, 128>, 4 * 256 * 64 * 2); break;   // phase profile into keep_bits (tools/attn_bench.py --prof)
+      case 1: rc = MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, false, 1); break;
+      case 2: rc = MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, false, 2); break;
+      case 4: rc = MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, false, 4); break;
+      case 6: rc = MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, false, 6); break;
+      case 7: rc = MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, false, 7); break;
+      case 8: rc = MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, false, 8); break;
+      case 16: rc = MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, false, 16); break;
+      case 24: rc = MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, false, 24); break;
+      case 31: rc = MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, false, 31); break;
+      case 63: rc = MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, false, 63); break;
+      case 95: rc = MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, false, 95); break;
+      case 127: rc = MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, false, 127); break;
+      case 32: rc = MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, false, 32); break;
+      case 128: rc = MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, false, 128); break;   // phase profile into keep_bits (tools/attn_bench.py --prof)
       default: mh_set_error("attention_stream: ablation %d not built (1 2 4 6 7 8 16 24 31)", g_attn_abl); return MH_ERR_UNSUPPORTED;
     }
   }
@@ -1310,20 +1322,21 @@ int stream_fwd_impl(const void* q, const void* k, const void* vt_perm, void* ctx
   // A/B: 8 = 128-key stages on the 16-wave block (first MFMA after 32 KB instead of 64 KB have landed, 64 KB of LDS per block), 9 = static
   // priority for the younger half of the waves, 10 = both
   else if (g_attn_stream >= 8 && full && !small && L <= qper && dh == 64)
-    rc = g_attn_stream == 8 ? go(&attn_stream_bf16_kernel<64, 16, 128, 0, true, true>, 4 * 128 * 64 * 2)
-       : g_attn_stream == 9 ? go(&attn_stream_bf16_kernel<64, 16, 256, 0, true, true, false, 0, 1>, 4 * 256 * 64 * 2)
-                            : go(&attn_stream_bf16_kernel<64, 16, 128, 0, true, true, false, 0, 1>, 4 * 128 * 64 * 2);
+    rc = g_attn_stream == 8 ? MH_STREAM_GO(4 * 128 * 64 * 2, 64, 16, 128, 0, true, true)
+       : g_attn_stream == 9 ? MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, false, 0, 1)
+                            : MH_STREAM_GO(4 * 128 * 64 * 2, 64, 16, 128, 0, true, true, false, 0, 1);
 #endif
   else if (full && !small && L <= qper)   // one block streams a (batch, head)'s K / V once: nt policy
-    rc = dh == 64 ? go(&attn_stream_bf16_kernel<64, 16, 256, 0, true, true>, 4 * 256 * 64 * 2) : go(&attn_stream_bf16_kernel<32, 16, 256, 0, true, true>, 4 * 256 * 32 * 2);
-  else if (full && dh == 64) rc = small ? go(&attn_stream_bf16_kernel<64, 8, 128, 0, true>, 4 * 128 * 64 * 2) : go(&attn_stream_bf16_kernel<64, 16, 256, 0, true>, 4 * 256 * 64 * 2);
-  else if (full) rc = small ? go(&attn_stream_bf16_kernel<32, 8, 256, 0, true>, 4 * 256 * 32 * 2) : go(&attn_stream_bf16_kernel<32, 16, 256, 0, true>, 4 * 256 * 32 * 2);
-  else if (dh == 64) rc = small ? go(&attn_stream_bf16_kernel<64, 8, 128>, 4 * 128 * 64 * 2) : go(&attn_stream_bf16_kernel<64, 16, 256>, 4 * 256 * 64 * 2);
-  else rc = small ? go(&attn_stream_bf16_kernel<32, 8, 256>, 4 * 256 * 32 * 2) : go(&attn_stream_bf16_kernel<32, 16, 256>, 4 * 256 * 32 * 2);
+    rc = dh == 64 ? MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true) : MH_STREAM_GO(4 * 256 * 32 * 2, 32, 16, 256, 0, true, true);
+  else if (full && dh == 64) rc = small ? MH_STREAM_GO(4 * 128 * 64 * 2, 64, 8, 128, 0, true) : MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true);
+  else if (full) rc = small ? MH_STREAM_GO(4 * 256 * 32 * 2, 32, 8, 256, 0, true) : MH_STREAM_GO(4 * 256 * 32 * 2, 32, 16, 256, 0, true);
+  else if (dh == 64) rc = small ? MH_STREAM_GO(4 * 128 * 64 * 2, 64, 8, 128) : MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256);
+  else rc = small ? MH_STREAM_GO(4 * 256 * 32 * 2, 32, 8, 256) : MH_STREAM_GO(4 * 256 * 32 * 2, 32, 16, 256);
   if (rc) return rc;
   MH_CHECK_LAUNCH();
   return MH_OK;
 }
+#undef MH_STREAM_GO
 }  // namespace
 
 #ifdef MH_ABLATE

@@ -2,10 +2,11 @@
 
 * `philox7` / `dense_keep`: the dense dropout sites' keep flags restated on the host (numpy) - Philox4x32-7 keyed by the seed at counter
   ((row N + col) / 8, offset), 16 bits per element (csrc/common.h: drop_keep8).
-* `record`: runs a callable with the library's per-launch recorder on (mh_profile_start / mh_profile_stop) and returns the GEMM-family
+* `record` (`record_family` for another kernel family: tests/attention_census.py): runs a callable with the library's per-launch recorder on (mh_profile_start / mh_profile_stop) and returns the GEMM-family
   launches as census keys: the kernel's template text as launched (it carries EPI, ACT, the epilogue form and the DMA bits) plus the
   `tile=` field of the launch note (which config `C` stood for).  Never call it inside a hipGraph capture.
-* `WORKLOADS`: the eager runs the census records, at the shapes bench.py uses (dispatch depends on M)."""
+* `WORKLOADS`: the eager runs the census records, at the shapes bench.py uses (dispatch depends on M); `run(dev, rec)` records with `rec`
+  (default: `record`)."""
 import ctypes
 
 import numpy as np
@@ -58,6 +59,12 @@ def census_key(kernel, note):
 
 def record(fn):
     """fn() with the per-launch recorder on -> [(key, note)] of its GEMM-family launches, in launch order"""
+    return [(k, note) for k, note, _ in record_family(fn, census_key)]
+
+
+def record_family(fn, key_of):
+    """fn() with the per-launch recorder on -> [(key, note, grid)] of the launches `key_of(kernel text, note)` gives a key (not None), in
+    launch order; grid = blocks in x, as launched"""
     import torch
     from musediffusion_amd import _lib
     lib = _lib.lib()
@@ -70,16 +77,16 @@ def record(fn):
         buf = ctypes.create_string_buffer(1 << 24)
         need = lib.mh_profile_stop(buf, len(buf))
     assert 0 < need <= len(buf), need
-    return _parse(buf.value.decode())
+    return _parse(buf.value.decode(), key_of)
 
 
-def _parse(text):
+def _parse(text, key_of=census_key):
     out = []
     for line in text.splitlines():
-        kernel, note = line.split("\t")[:2]
-        k = census_key(kernel, note)
+        kernel, note, grid = line.split("\t")[:3]
+        k = key_of(kernel, note)
         if k is not None:
-            out.append((k, note))
+            out.append((k, note, int(grid)))
     return out
 
 
@@ -95,7 +102,7 @@ def _bench():
 
 
 def _forward(workload, dtype):
-    def run(dev):
+    def run(dev, rec=record):
         import torch
         bench = _bench()
         c = bench.WORKLOADS[workload]
@@ -104,13 +111,13 @@ def _forward(workload, dtype):
         x = torch.randn(c["B"], c["L"], c["E"], generator=g).to(dev)
         t = torch.randint(0, c["T"], (c["B"],), generator=g).to(dev)
         with torch.no_grad():
-            return record(lambda: model(x, t))
+            return rec(lambda: model(x, t))
     return run
 
 
 def _reverse_step(workload):
     """one eager p_sample step with the nearest-embedding rounding: the captured step's launches, run one by one"""
-    def run(dev):
+    def run(dev, rec=record):
         import torch
         bench = _bench()
         c = bench.WORKLOADS[workload]
@@ -119,7 +126,7 @@ def _reverse_step(workload):
         loop = bench.make_loop(model, diff, c, "p", dev, 0, 2)
         with torch.no_grad():
             loop.begin()
-            keys = record(lambda: loop.advance(0))
+            keys = rec(lambda: loop.advance(0))
             loop.finish()
         return keys
     return run
@@ -127,7 +134,7 @@ def _reverse_step(workload):
 
 def _train(workload, p, B=None, L=None):
     """one training micro-step (training_losses forward + backward) in train mode with dropout p"""
-    def run(dev):
+    def run(dev, rec=record):
         import torch
         from musediffusion_amd import synthetic
         bench = _bench()
@@ -144,7 +151,7 @@ def _train(workload, p, B=None, L=None):
             model.zero_grad(set_to_none=True)
             diff.training_losses(model, t, model_kwargs=batch)["loss"].mean().backward()
         step()          # (lazy weight preparation and workspaces outside the recorded step)
-        return record(step)
+        return rec(step)
     return run
 
 
