@@ -1,6 +1,8 @@
 // Unmasked multi-head self-attention, flash style (the L x L scores never reach memory).
 // Reference op group: HF BertSelfAttention reached from models/network.py:151 — no mask is ever
 // passed (diffusion.py:309 / :624 drop model_kwargs), attention runs over padding too.
+// This object: the kernels for any seq_len % 8 == 0 (mh_attention_fwd / _ex).  The streaming forward that serves seq_len >= 512 is
+// attn_stream.h / attention_stream.hip, the backward attention_bwd.hip.
 //
 // bf16 kernel (CDNA4): one workgroup = 4 waves = 128 queries of one (batch, head); each wave owns 32
 // queries and walks the keys in tiles of 64.
@@ -18,9 +20,6 @@
 // f32 kernel: plain VALU fp32 (the f32 MFMA rate equals the VALU rate on gfx950), 64 queries per
 // workgroup, exact expf; this is the parity path, kept simple on purpose.
 #include <type_traits>
-
-#include <mutex>
-#include <set>
 
 #include "common.h"
 
@@ -545,571 +544,14 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const float* __restrict__
   }
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// Streaming attention (bf16, L a multiple of 256, >= 512 queries per block): persistent blocks of 16 waves, one
-// 32-query tile per wave, K / V^T streamed through LDS in 256-key stages by LDS-DMA, double-buffered - the
-// stage (or the next (batch, head)) after the current one is in flight while the current one is computed, so
-// the HBM traffic is spread over the whole kernel instead of arriving as one burst per block before any MFMA
-// can start (the LDS-resident kernel above spends 10 of its 33 us per block in that burst at L = 512).
-// V^T arrives in the "P-operand" key order (mh_gemm_qkv_vtperm): within every 16 keys the two middle groups of
-// four are swapped, which is the order the S^T accumulator registers hold the probabilities in, so a stage
-// is a straight 16-byte-granular copy (source-side XOR swizzle) and P feeds the P.V MFMA without a shuffle.
-// DROP (training): attention-probability dropout (HF BertSelfAttention: softmax -> dropout -> . V).  The keep flags of the
-// wave's 32 x 32 S^T sub-tile come from Philox (drop_keep_attn) and are written to `keep_bits` (lane-native words, common.h
-// drop_word_index: one store per lane and 64-key tile) for the backward kernels - or, with bits_in, are read from it (mask injection).
-// The softmax normaliser runs over the un-dropped probabilities; 1 / (1 - p) is folded into the final 1 / l.
-// DROP: 0 = no dropout, 1 = generate the keep flags (Philox) and write the bit tensor, 2 = read the bit tensor (a pre-pass or a test
-// wrote it): the reading variant needs no generator registers and fits the 16-wave geometry
-// FULL: seq_len is a multiple of SK, so no stage or tile is partial - the key-bound compares (which hipcc if-converts into a compare
-// + select per score of EVERY tile, a third of the tile's vector instructions) are compiled out.  (The bit reader keeps the
-// key-bound body: its bound-free build spills 60 B per lane and measured 5 % slower, as did staging its keep words in LDS.)
-// KVNT: the K / V stage DMA with the nt cache policy (aux 2) - chosen when a (batch, head)'s keys and values are streamed by ONE
-// block and never again (seq_len <= the block's queries): same-box A/B of two builds -1.2 % step time at config 2; with two query
-// blocks per (batch, head) (seq_len 1024) the second reader misses them: +0.4 % on the training step, so the default policy there
-// PRE: the queries arrive pre-multiplied by scale x log2(e) (the QKV epilogue folds it in, mh_gemm_qkv_vtperm_qs), so the S^T
-// accumulators are already in the log2 domain, and the running reference lives in their INITIAL value: the first MFMA of every S^T
-// chain takes C = -reference (16 registers that change only when the reference moves), so a probability is exp2(accumulator) with
-// no multiply-subtract per score - 32 of the ~170 vector instructions of a 64-key tile (the kernel is VALU-bound)
-// ABL: timing-only ablations (tools/attn_bench.py --ablate; results are garbage): 1 no softmax vector work, 2 no S^T MFMAs, 4 no P.V MFMAs,
-// 8 no LDS fragment reads, 16 no K / V stage DMA
-// PRIO (A/B, mh_attention_set_stream 9 / 10): one static s_setprio 1 for the younger half of the block's waves (MI355X_MICROARCH.md, two waves
-// per SIMD, item 4: the later-dispatched waves lose every issue arbitration at equal priority)
-template <int DH, int NW = 16, int SK = 256, int DROP = 0, bool FULL = false, bool KVNT = false, bool PRE = false, int ABL = 0, int PRIO = 0>
-__global__ __launch_bounds__(64 * NW) void attn_stream_bf16_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K,
-                                                                const bf16* __restrict__ VT, bf16* __restrict__ ctx,
-                                                                int64_t ld_ctx, int L, int nh, int nbh, float scale_log2e,
-                                                                int ctx_panel, float* __restrict__ lse2, int64_t qsB, int64_t qsH, int64_t qld,
-                                                                const DropArgs drop, uint32_t* __restrict__ keep_bits, int bits_in) {
-  // NW waves (one 32-query tile each), SK keys per stage.  16 x 256 fills a CU (128 KiB LDS, four waves per SIMD); 8 x 128
-  // leaves half of the CU's registers and LDS for a GEMM block of the other graph branch
-  constexpr int CH = DH / 8, RPB = 128 / DH, KROWB = DH * 2;
-  constexpr int KS = DH / 16, DT = DH / 32;
-  constexpr int KST = SK * KROWB, VT_BYTES = DH * 128;   // K stage bytes (= V stage bytes), V^T bytes per 64-key tile
-  constexpr int PK = KST / 1024 / NW;                    // 1-KiB DMA pieces per wave per operand per stage
-  constexpr int KRP = 1024 / KROWB;                      // K rows per piece
-  static_assert(PK >= 1, "stage too small for the wave count");
-  extern __shared__ __attribute__((aligned(16))) char smem_dyn[];
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int h = lane >> 5, lq = lane & 31;
-  if constexpr (PRIO != 0) { if (wave >= NW / 2) __builtin_amdgcn_s_setprio(1); }
-  const int nqb = (L + 32 * NW - 1) / (32 * NW), nst = (L + SK - 1) / SK;   // the last stage / tile may be partial (L % 16 == 0)
-  const int nitems = nbh * nqb;
-  // XCD-aware item order (round 6): the query blocks of one (batch, head) (two at seq_len 1024, five at 2096) stream the same K / V^T
-  // and should meet in one L2; at seq_len 512 (one block per (batch, head)) the order changes nothing
-  const int bx = mh_xcd_remap((int)blockIdx.x, (int)gridDim.x);
-  const int my_items = (nitems - bx + (int)gridDim.x - 1) / (int)gridDim.x;
-  const int total = my_items * nst;
-
-  auto issue = [&](int g) {   // DMA stage g (of this block's flattened (item, stage) sequence) into buffer g & 1
-    if constexpr ((ABL & 16) != 0) return;
-    const int item = bx + (g / nst) * gridDim.x, st = g % nst;
-    const int bh = item / nqb;
-    const bf16* Kb = K + (int64_t)(bh / nh) * qsB + (int64_t)(bh % nh) * qsH + (int64_t)st * SK * qld;   // rows qld elements apart
-    const bf16* Vb = VT + (int64_t)bh * DH * L + (int64_t)st * SK;
-    char* kdst = smem_dyn + (g & 1) * (2 * KST);
-    char* vdst = kdst + KST;
-#pragma unroll
-    for (int j = 0; j < PK; ++j) {
-      const int p = wave + NW * j;
-      const int row = p * KRP + lane / CH, pc = lane % CH;             // key within the stage, physical chunk
-      const int lc = pc ^ ((row / RPB) & (CH - 1));
-      int rsrc = row;                                                   // keys past the end: any valid row (their scores are masked)
-      if (!FULL && st * SK + row >= L) rsrc = L - 1 - st * SK;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(Kb + (int64_t)rsrc * qld + lc * 8),
-                                       (__attribute__((address_space(3))) void*)(kdst + p * 1024), 16, 0, KVNT ? 2 : 0);
-    }
-#pragma unroll
-    for (int j = 0; j < PK; ++j) {
-      const int p = wave + NW * j;
-      const int t = p / (DH / 8), d = (p % (DH / 8)) * 8 + (lane >> 3), pc = lane & 7;
-      const int lc = pc ^ ((d >> 1) & 7);
-      int kc = t * 64 + lc * 8;                                         // 8 keys past the end: any valid chunk (finite values x P = 0)
-      if (!FULL && st * SK + kc >= L) kc = L - 8 - st * SK;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(Vb + (int64_t)d * L + kc),
-                                       (__attribute__((address_space(3))) void*)(vdst + p * 1024), 16, 0, KVNT ? 2 : 0);
-    }
-  };
-
-  const int ksw0 = (lq / RPB) & (CH - 1), ksw1 = ((32 + lq) / RPB) & (CH - 1);
-  bf16x8 qf[KS];
-  f32x16 o[DT];
-  float m_run = -INFINITY, l_run = 0.f;
-  f32x16 sinit;              // PRE: -reference (log2 domain) in every register
-  bool first_tile = false;   // PRE: no reference yet (wave-uniform)
-#pragma unroll
-  for (int r = 0; r < 16; ++r) sinit[r] = 0.f;
-  int q0 = 0;
-  bool active = false;
-
-  unsigned long long prof_acc[4] = {0, 0, 0, 0};
-  if (total > 0) issue(0);
-  for (int g = 0; g < total; ++g) {
-    const int item = bx + (g / nst) * gridDim.x, st = g % nst;
-    const int bh = item / nqb, qb = item % nqb;
-    unsigned long long tp0 = 0, tp1 = 0, tp2 = 0;      // ABL bit 128: where a wave's time goes (clock stamps per stage, summed per wave)
-    if constexpr ((ABL & 128) != 0) tp0 = __builtin_amdgcn_s_memtime();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // stage g (issued one stage ago) has landed
-    if constexpr ((ABL & 128) != 0) tp1 = __builtin_amdgcn_s_memtime();
-    __builtin_amdgcn_s_barrier();                      // ... for every wave; buffer (g+1)&1 was released at the end of stage g-1
-    if constexpr ((ABL & 128) != 0) tp2 = __builtin_amdgcn_s_memtime();
-    if (g + 1 < total) issue(g + 1);
-    if (st == 0) {
-      q0 = qb * (32 * NW) + wave * 32;
-      active = q0 < L;
-      if (active) {
-        const bf16* Qb = Q + (int64_t)(bh / nh) * qsB + (int64_t)(bh % nh) * qsH;
-        int qr = q0 + lq; if (qr >= L) qr = L - 1;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-          if constexpr ((ABL & 64) != 0) { for (int j = 0; j < 8; ++j) qf[ks][j] = (bf16)(0.01f * (j + ks) + 0.001f * lq); }
-          else qf[ks] = *reinterpret_cast<const bf16x8*>(Qb + (int64_t)qr * qld + 16 * ks + 8 * h);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < DT; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[i][r] = 0.f;
-      m_run = -INFINITY; l_run = 0.f;
-      if constexpr (PRE) {
-        m_run = 0.f; first_tile = true;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sinit[r] = 0.f;
-      }
-    }
-    if (active) {
-      const char* kbuf = smem_dyn + (g & 1) * (2 * KST);
-      const char* vbuf = kbuf + KST;
-      const int st_keys = L - st * SK;                                  // valid keys of this stage (>= 16)
-      if constexpr (PRE) {
-        // pre-scaled queries: 32-key sub-tiles, one S^T accumulator set live at a time (the 16 registers that freed hold the initial
-        // accumulator = -reference).  The accumulators come out as score - reference in the log2 domain, so p = exp2(accumulator).
-        for (int t2 = 0; t2 < SK / 32 && (FULL || t2 * 32 < st_keys); ++t2) {
-          const int t = t2 >> 1, kt = t2 & 1;
-          const char* kb = kbuf + t * (64 * KROWB);
-          const char* vb = vbuf + t * VT_BYTES;
-          const int sub_keys = FULL ? 32 : st_keys - t2 * 32;             // < 32 only in the sequence's last sub-tile
-          f32x16 sa;
-          {
-            bf16x8 kf[KS];
-            const int krow = 32 * kt + lq, ksw = kt ? ksw1 : ksw0;
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) kf[ks] = *reinterpret_cast<const bf16x8*>(kb + krow * KROWB + (((2 * ks + h) ^ ksw) << 4));
-            // the chain's first MFMA reads its C operand from the initial-accumulator registers and writes the accumulator itself
-            // (D != C): as a builtin hipcc copies the 16 registers first, which costs what the multiply-subtract did
-            asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %3" : "=&v"(sa) : "v"(kf[0]), "v"(qf[0]), "v"(sinit));
-#pragma unroll
-            for (int ks = 1; ks < KS; ++ks) sa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[ks], qf[ks], sa, 0, 0, 0);
-          }
-          if (!FULL && sub_keys < 32) {   // register r holds key (r & 3) + 8 (r >> 2) + 4 h of the sub-tile: mask the ones past the end
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-              if ((r & 3) + 8 * (r >> 2) + 4 * h >= sub_keys) sa[r] = -INFINITY;
-          }
-          // the row maximum of the 16 scores as ONE asm statement of v_max3 (fmaxf on MFMA outputs makes hipcc canonicalise every
-          // input with a v_max first: 16 more instructions).  hipcc pads no hazard whose consumer sits inside an asm string: the
-          // 12 wait states an 8-pass MFMA result needs before a VALU read open the string (cdna_hip_programming.md 5.7 item 2)
-          float mx, mt1, mt2, mt3, mt4;
-          asm volatile("s_nop 11\n\t"
-                       "v_max3_f32 %0, %5, %6, %7\n\t"
-                       "v_max3_f32 %1, %8, %9, %10\n\t"
-                       "v_max3_f32 %2, %11, %12, %13\n\t"
-                       "v_max3_f32 %3, %14, %15, %16\n\t"
-                       "v_max3_f32 %4, %17, %18, %19\n\t"
-                       "v_max3_f32 %0, %0, %1, %2\n\t"
-                       "v_max3_f32 %1, %3, %4, %20\n\t"
-                       "v_max_f32 %0, %0, %1"
-                       : "=&v"(mx), "=&v"(mt1), "=&v"(mt2), "=&v"(mt3), "=&v"(mt4)
-                       : "v"(sa[0]), "v"(sa[1]), "v"(sa[2]), "v"(sa[3]), "v"(sa[4]), "v"(sa[5]), "v"(sa[6]), "v"(sa[7]), "v"(sa[8]), "v"(sa[9]),
-                         "v"(sa[10]), "v"(sa[11]), "v"(sa[12]), "v"(sa[13]), "v"(sa[14]), "v"(sa[15]));
-          mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-          // the reference moves by `shift` when a row overshoots it by more than 2^8 (or on the item's first sub-tile, where it
-          // becomes the sub-tile maximum): this sub-tile's accumulators, the running sum and the output are re-based
-          if (first_tile || __builtin_amdgcn_ballot_w64(mx > 8.0f) != 0) {
-            const float shift = first_tile ? mx : fmaxf(mx, 0.f);
-            if (!first_tile) {
-              const float alpha = __builtin_amdgcn_exp2f(-shift);
-              l_run *= alpha;
-#pragma unroll
-              for (int i = 0; i < DT; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o[i][r] *= alpha;
-            }
-            m_run += shift;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sa[r] -= shift;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sinit[r] = -m_run;
-            first_tile = false;
-          }
-#pragma unroll
-          for (int r = 0; r < 16; ++r) sa[r] = __builtin_amdgcn_exp2f(sa[r]);
-          float ps4[4] = {sa[0], sa[1], sa[2], sa[3]};
-#pragma unroll
-          for (int r = 4; r < 16; ++r) ps4[r & 3] += sa[r];
-          l_run += (ps4[0] + ps4[1]) + (ps4[2] + ps4[3]);
-#pragma unroll
-          for (int s2 = 0; s2 < 2; ++s2) {
-            bf16x8 pf;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) pf[j] = (bf16)sa[8 * s2 + j];
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt) {
-              const int d = dt * 32 + lq;
-              const bf16x8 vf = *reinterpret_cast<const bf16x8*>(vb + d * 128 + (((2 * (2 * kt + s2) + h) ^ ((d >> 1) & 7)) << 4));
-              o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, o[dt], 0, 0, 0);
-            }
-          }
-        }
-      } else
-      for (int t = 0; t < SK / 64 && (FULL || t * 64 < st_keys); ++t) {
-        const char* kb = kbuf + t * (64 * KROWB);
-        const char* vb = vbuf + t * VT_BYTES;
-        const int tile_keys = FULL ? 64 : st_keys - t * 64;             // < 64 only in the sequence's last tile
-        f32x16 s[2];
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt) {
-          bf16x8 kf[KS];
-          const int krow = 32 * kt + lq, ksw = kt ? ksw1 : ksw0;
-#pragma unroll
-          for (int ks = 0; ks < KS; ++ks) {
-            if constexpr ((ABL & 8) != 0) kf[ks] = qf[(ks + 1) % KS];
-            else kf[ks] = *reinterpret_cast<const bf16x8*>(kb + krow * KROWB + (((2 * ks + h) ^ ksw) << 4));
-          }
-#pragma unroll
-          for (int r = 0; r < 16; ++r) s[kt][r] = (ABL & 2) ? 0.01f * r + (float)kf[0][r & 7] : 0.f;
-          if constexpr ((ABL & 2) == 0) {
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[ks], qf[ks], s[kt], 0, 0, 0);
-          }
-        }
-        if (!FULL && tile_keys < 64) {   // register r of sub-tile kt holds key 32 kt + (r & 3) + 8 (r >> 2) + 4 h: mask the ones past the end
-#pragma unroll
-          for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-              if (kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h >= tile_keys) s[kt][r] = -INFINITY;
-        }
-        if constexpr ((ABL & 1) == 0) {
-        float mx4[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-          for (int r = 0; r < 16; r += 4)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) mx4[e] = fmaxf(mx4[e], s[kt][r + e]);
-        float mx = fmaxf(fmaxf(mx4[0], mx4[1]), fmaxf(mx4[2], mx4[3]));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        // lazy rescale: the running reference m_run only moves when some row's tile maximum exceeds it by more than
-        // 2^8 in the exponent domain (always on the first tile, where it is -inf); otherwise the probabilities are
-        // taken against the stale reference (p <= 256, harmless in fp32 / bf16) and the 32 accumulator multiplies,
-        // the exp of alpha and the l_run multiply are skipped.  The final o / l is unchanged up to rounding.
-        if (__builtin_amdgcn_ballot_w64((mx - m_run) * scale_log2e > 8.0f) != 0) {
-          const float m_new = fmaxf(m_run, mx);
-          const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * scale_log2e);
-          l_run *= alpha;
-          m_run = m_new;
-#pragma unroll
-          for (int i = 0; i < DT; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[i][r] *= alpha;
-        }
-        const float mb = m_run * scale_log2e;
-        float ps4[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const float p = __builtin_amdgcn_exp2f(s[kt][r] * scale_log2e - mb);
-            s[kt][r] = p;
-            ps4[r & 3] += p;
-          }
-        l_run += (ps4[0] + ps4[1]) + (ps4[2] + ps4[3]);
-        }
-        if constexpr (DROP != 0) {
-          const int nb32 = (L + 31) >> 5;
-          const int64_t wi = drop_word_index(bh, nb32, q0 >> 5, (st * SK + t * 64) >> 6, lane);   // this lane's word of the 64-key tile
-          uint32_t kw;
-          if constexpr (DROP == 2) {
-            kw = keep_bits[wi];
-          } else {
-            const int qc = q0 + lq < L ? q0 + lq : L - 1;
-            const int kb = (st * SK + t * 64) >> 5;
-            kw = drop_keep_attn(drop, bh, L, nb32, qc, kb, h);
-            if (FULL || 32 < tile_keys) kw |= drop_keep_attn(drop, bh, L, nb32, qc, kb + 1, h) << 16;   // (wave-uniform)
-            keep_bits[wi] = kw;
-          }
-#pragma unroll
-          for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s[kt][r] = and_bits(s[kt][r], keep_mask(kw, 16 * kt + r));
-        }
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-          for (int s2 = 0; s2 < 2; ++s2) {
-            bf16x8 pf;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) pf[j] = (bf16)s[kt][8 * s2 + j];
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt) {
-              const int d = dt * 32 + lq;
-              bf16x8 vf;
-              if constexpr ((ABL & 8) != 0) vf = qf[(dt + s2) % KS];
-              else vf = *reinterpret_cast<const bf16x8*>(vb + d * 128 + (((2 * (2 * kt + s2) + h) ^ ((d >> 1) & 7)) << 4));
-              if constexpr ((ABL & 4) != 0) asm volatile("" ::"v"(vf), "v"(pf));
-              else o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, o[dt], 0, 0, 0);
-            }
-          }
-      }
-      if (st == nst - 1) {   // last stage of this (batch, head): normalise and write the context rows
-        const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-        const float inv = (DROP != 0 ? drop.rscale : 1.0f) / l_tot;
-        const int qr = q0 + lq;
-        {
-          const int b = bh / nh, head = bh % nh;
-          const int64_t tok = (int64_t)b * L + (qr < L ? qr : L - 1);
-          // log2-domain log-sum-exp of the scaled scores: P[q][k] = exp2(s c - lse2[q]) (what the backward kernels re-create P from)
-          if (lse2 && h == 0 && qr < L) lse2[(int64_t)bh * L + qr] = (PRE ? m_run : m_run * scale_log2e) + __builtin_amdgcn_logf(l_tot);
-          // a lane holds 4 consecutive head-dim elements (8 B) of its query's row per group rg, its half-wave partner the next 4: one
-          // v_permlane32_swap per dword and pair of groups gives every lane 16 contiguous bytes, so the row leaves in 2 instead of 4
-          // stores per 32-column block (the store tail is issue-bound: cdna_hip_programming.md T21).  All lanes take part in the
-          // swaps (queries past the end hold finite garbage and do not store); 8-byte stores where the context rows are not 16-B aligned
-          const bool wide = ctx_panel || (ld_ctx % 8 == 0 && (reinterpret_cast<uintptr_t>(ctx) & 15) == 0);   // (wave-uniform)
-#pragma unroll
-          for (int dt = 0; dt < DT; ++dt) {
-            bf16* dst = ctx_panel ? ctx + (((int64_t)(head * DT + dt)) * ld_ctx + tok) * 32 : ctx + tok * ld_ctx + head * DH + dt * 32;
-            uint2 pk[4];
-#pragma unroll
-            for (int rg = 0; rg < 4; ++rg) {
-              bf16x4 v;
-#pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] = (bf16)(o[dt][rg * 4 + e] * inv);
-              __builtin_memcpy(&pk[rg], &v, 8);
-            }
-            if constexpr ((ABL & 32) != 0) { if (pk[0].x == 0x12345678u) *reinterpret_cast<uint2*>(dst + 4 * h) = pk[0]; }
-            else if (wide) {
-#pragma unroll
-              for (int k = 0; k < 4; k += 2) {
-                uint2 a = pk[k], b = pk[k + 1];
-                auto rx = __builtin_amdgcn_permlane32_swap(a.x, b.x, false, false);
-                auto ry = __builtin_amdgcn_permlane32_swap(a.y, b.y, false, false);
-                if (qr < L) *reinterpret_cast<uint4*>(dst + 8 * k + 8 * h) = uint4{rx[0], ry[0], rx[1], ry[1]};
-              }
-            } else if (qr < L) {
-#pragma unroll
-              for (int rg = 0; rg < 4; ++rg) *reinterpret_cast<uint2*>(dst + 8 * rg + 4 * h) = pk[rg];
-            }
-          }
-        }
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if constexpr ((ABL & 128) != 0) {
-      const unsigned long long tp3 = __builtin_amdgcn_s_memtime();
-      __builtin_amdgcn_s_barrier();
-      const unsigned long long tp4 = __builtin_amdgcn_s_memtime();
-      prof_acc[0] += tp1 - tp0; prof_acc[1] += tp2 - tp1; prof_acc[2] += tp3 - tp2; prof_acc[3] += tp4 - tp3;
-      if (g == total - 1 && lane == 0) {   // per (block, wave): DMA wait, top barrier, stage work, bottom barrier (shader clocks)
-        unsigned long long* dstp = reinterpret_cast<unsigned long long*>(keep_bits) + ((size_t)blockIdx.x * NW + wave) * 4;
-        dstp[0] = prof_acc[0]; dstp[1] = prof_acc[1]; dstp[2] = prof_acc[2]; dstp[3] = prof_acc[3];
-      }
-    } else
-    __builtin_amdgcn_s_barrier();                      // every wave is done reading buffer g & 1
-  }
-}
-
-// Streaming attention with TWO 32-query tiles per wave (8 waves x 64 queries = one 512-query item per block, 2 waves per SIMD at 256
-// registers): a K fragment read from LDS feeds the S^T chains of both query tiles and a V^T fragment both P.V products, so the
-// 2 MB of fragment reads per (batch, head) of the 16-wave form - every wave re-reads all of K and V - halve (its ablation: 5.9 of 27.8 us
-// per half-batch launch are those reads).  Same stages (256 keys, double-buffered LDS-DMA), same swizzles, same lazy-rescale softmax and
-// store path as attn_stream_bf16_kernel; head dim 64, seq_len % 256 == 0, no dropout.  A/B: mh_attention_set_stream(7).
-template <bool KVNT>
-__global__ __launch_bounds__(512, 2) void attn_stream2_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ K, const bf16* __restrict__ VT,
-                                                              bf16* __restrict__ ctx, int64_t ld_ctx, int L, int nh, int nbh, float scale_log2e,
-                                                              int ctx_panel, int64_t qsB, int64_t qsH, int64_t qld) {
-  constexpr int DH = 64, NW = 8, SK = 256, QT = 2;
-  constexpr int CH = DH / 8, RPB = 128 / DH, KROWB = DH * 2, KS = DH / 16, DT = DH / 32;
-  constexpr int KST = SK * KROWB, VT_BYTES = DH * 128, PK = KST / 1024 / NW, KRP = 1024 / KROWB;
-  extern __shared__ __attribute__((aligned(16))) char smem_dyn[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int h = lane >> 5, lq = lane & 31;
-  const int nqb = L / (32 * NW * QT), nst = L / SK;
-  const int nitems = nbh * nqb;
-  const int my_items = (nitems - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
-  const int total = my_items * nst;
-  auto issue = [&](int g) {
-    const int item = blockIdx.x + (g / nst) * gridDim.x, st = g % nst;
-    const int bh = item / nqb;
-    const bf16* Kb = K + (int64_t)(bh / nh) * qsB + (int64_t)(bh % nh) * qsH + (int64_t)st * SK * qld;
-    const bf16* Vb = VT + (int64_t)bh * DH * L + (int64_t)st * SK;
-    char* kdst = smem_dyn + (g & 1) * (2 * KST);
-    char* vdst = kdst + KST;
-#pragma unroll
-    for (int j = 0; j < PK; ++j) {
-      const int p = wave + NW * j;
-      const int row = p * KRP + lane / CH, pc = lane % CH;
-      const int lc = pc ^ ((row / RPB) & (CH - 1));
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(Kb + (int64_t)row * qld + lc * 8),
-                                       (__attribute__((address_space(3))) void*)(kdst + p * 1024), 16, 0, KVNT ? 2 : 0);
-    }
-#pragma unroll
-    for (int j = 0; j < PK; ++j) {
-      const int p = wave + NW * j;
-      const int t = p / (DH / 8), d = (p % (DH / 8)) * 8 + (lane >> 3), pc = lane & 7;
-      const int lc = pc ^ ((d >> 1) & 7);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(Vb + (int64_t)d * L + t * 64 + lc * 8),
-                                       (__attribute__((address_space(3))) void*)(vdst + p * 1024), 16, 0, KVNT ? 2 : 0);
-    }
-  };
-  const int ksw0 = (lq / RPB) & (CH - 1), ksw1 = ((32 + lq) / RPB) & (CH - 1);
-  bf16x8 qf[QT][KS];
-  f32x16 o[QT][DT];
-  float m_run[QT], l_run[QT];
-  int q0 = 0;
-  if (total > 0) issue(0);
-  for (int g = 0; g < total; ++g) {
-    const int item = blockIdx.x + (g / nst) * gridDim.x, st = g % nst;
-    const int bh = item / nqb, qb = item % nqb;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (g + 1 < total) issue(g + 1);
-    if (st == 0) {
-      q0 = qb * (32 * NW * QT) + wave * (32 * QT);
-      const bf16* Qb = Q + (int64_t)(bh / nh) * qsB + (int64_t)(bh % nh) * qsH;
-#pragma unroll
-      for (int qt = 0; qt < QT; ++qt) {
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) qf[qt][ks] = *reinterpret_cast<const bf16x8*>(Qb + (int64_t)(q0 + 32 * qt + lq) * qld + 16 * ks + 8 * h);
-#pragma unroll
-        for (int i = 0; i < DT; ++i)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) o[qt][i][r] = 0.f;
-        m_run[qt] = -INFINITY; l_run[qt] = 0.f;
-      }
-    }
-    const char* kbuf = smem_dyn + (g & 1) * (2 * KST);
-    const char* vbuf = kbuf + KST;
-    for (int t = 0; t < SK / 64; ++t) {
-      const char* kb = kbuf + t * (64 * KROWB);
-      const char* vb = vbuf + t * VT_BYTES;
-      f32x16 s[QT][2];
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt) {
-        bf16x8 kf[KS];
-        const int krow = 32 * kt + lq, ksw = kt ? ksw1 : ksw0;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) kf[ks] = *reinterpret_cast<const bf16x8*>(kb + krow * KROWB + (((2 * ks + h) ^ ksw) << 4));
-#pragma unroll
-        for (int qt = 0; qt < QT; ++qt)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) s[qt][kt][r] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-          for (int qt = 0; qt < QT; ++qt) s[qt][kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[ks], qf[qt][ks], s[qt][kt], 0, 0, 0);
-      }
-#pragma unroll
-      for (int qt = 0; qt < QT; ++qt) {
-        float mx4[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-          for (int r = 0; r < 16; r += 4)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) mx4[e] = fmaxf(mx4[e], s[qt][kt][r + e]);
-        float mx = fmaxf(fmaxf(mx4[0], mx4[1]), fmaxf(mx4[2], mx4[3]));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        if (__builtin_amdgcn_ballot_w64((mx - m_run[qt]) * scale_log2e > 8.0f) != 0) {      // lazy rescale (see attn_stream_bf16_kernel)
-          const float m_new = fmaxf(m_run[qt], mx);
-          const float alpha = __builtin_amdgcn_exp2f((m_run[qt] - m_new) * scale_log2e);
-          l_run[qt] *= alpha;
-          m_run[qt] = m_new;
-#pragma unroll
-          for (int i = 0; i < DT; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[qt][i][r] *= alpha;
-        }
-        const float mb = m_run[qt] * scale_log2e;
-        float ps4[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const float p = __builtin_amdgcn_exp2f(s[qt][kt][r] * scale_log2e - mb);
-            s[qt][kt][r] = p;
-            ps4[r & 3] += p;
-          }
-        l_run[qt] += (ps4[0] + ps4[1]) + (ps4[2] + ps4[3]);
-      }
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          bf16x8 pf[QT];
-#pragma unroll
-          for (int qt = 0; qt < QT; ++qt)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) pf[qt][j] = (bf16)s[qt][kt][8 * s2 + j];
-#pragma unroll
-          for (int dt = 0; dt < DT; ++dt) {
-            const int d = dt * 32 + lq;
-            const bf16x8 vf = *reinterpret_cast<const bf16x8*>(vb + d * 128 + (((2 * (2 * kt + s2) + h) ^ ((d >> 1) & 7)) << 4));
-#pragma unroll
-            for (int qt = 0; qt < QT; ++qt) o[qt][dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[qt], o[qt][dt], 0, 0, 0);
-          }
-        }
-    }
-    if (st == nst - 1) {
-      const int b = bh / nh, head = bh % nh;
-#pragma unroll
-      for (int qt = 0; qt < QT; ++qt) {
-        const float l_tot = l_run[qt] + __shfl_xor(l_run[qt], 32, 64);
-        const float inv = 1.0f / l_tot;
-        const int64_t tok = (int64_t)b * L + q0 + 32 * qt + lq;
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) {
-          bf16* dst = ctx_panel ? ctx + (((int64_t)(head * DT + dt)) * ld_ctx + tok) * 32 : ctx + tok * ld_ctx + head * DH + dt * 32;
-          uint2 pk[4];
-#pragma unroll
-          for (int rg = 0; rg < 4; ++rg) {
-            bf16x4 v;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = (bf16)(o[qt][dt][rg * 4 + e] * inv);
-            __builtin_memcpy(&pk[rg], &v, 8);
-          }
-#pragma unroll
-          for (int k = 0; k < 4; k += 2) {
-            uint2 a = pk[k], bb = pk[k + 1];
-            auto rx = __builtin_amdgcn_permlane32_swap(a.x, bb.x, false, false);
-            auto ry = __builtin_amdgcn_permlane32_swap(a.y, bb.y, false, false);
-            *reinterpret_cast<uint4*>(dst + 8 * k + 8 * h) = uint4{rx[0], ry[0], rx[1], ry[1]};
-          }
-        }
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();                      // every wave is done reading buffer g & 1
-  }
-}
-
-MH_KNOB(int, g_attn_abl, 0);        // timing-only ablation of the streaming kernel (mh_attention_set_ablation)
-MH_KNOB(int, g_attn_resident, 1);
+MH_KNOB(int, g_attn_resident, 1);                     // 0 tiled only, 1 resident where it fits, 2 resident on 16 waves (mh_attention_set_variant)
 MH_KNOB(unsigned long long*, g_attn_prof, nullptr);   // diagnostic stamps (mh_attention_set_profile)
 
 template <int DH>
 int launch_f32(const float* q, const float* k, const float* vt, float* ctx, int64_t ld, int B, int L, int nh,
                float scale, hipStream_t s) {
   constexpr size_t bytes = (size_t)(2 * 64 * (DH + 4) + DH * 68 + 64 * 68) * sizeof(float);
-  static bool attr_set[MH_MAX_DEVICES] = {};   // hipFuncSetAttribute acts on the current device's copy of the kernel
-  const int dev = mh_current_device();
-  if (!attr_set[dev]) {
-    MH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_f32_kernel<DH>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    attr_set[dev] = true;
-  }
+  if (int rc = mh_allow_dynamic_lds((const void*)&attn_f32_kernel<DH>, bytes)) return rc;
   dim3 grid(ceil_div(L, 64), B * nh), block(256);
   mh_prof_note("attn_small kind=f32 B*nh=%d L=%d dh=%d", B * nh, L, DH);
   MH_LAUNCH((attn_f32_kernel<DH>), grid, block, bytes, s, q, k, vt, ctx, ld, L, nh, scale);
@@ -1120,253 +562,46 @@ int launch_f32(const float* q, const float* k, const float* vt, float* ctx, int6
 template <int DH>
 int launch_bf16(const bf16* q, const bf16* k, const bf16* vt, bf16* ctx, int64_t ld, int B, int L, int nh,
                 float scale, int ctx_panel, hipStream_t s) {
-  const size_t res_bytes = (size_t)ceil_div(L, 64) * 64 * DH * 4;   // K + V^T of one (batch, head)
-  if (g_attn_resident && DH <= 64 && res_bytes <= 128 * 1024 && L >= 128) {
-    static bool attr_set[MH_MAX_DEVICES] = {};
-    const int dev = mh_current_device();
-    if (!attr_set[dev]) {
-      MH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_res_bf16_kernel<DH, 8>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-      MH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_res_bf16_kernel<DH, 16>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-      attr_set[dev] = true;
+  const float sl2 = scale * 1.4426950408889634f;
+  if constexpr (DH <= 64) {   // (the resident kernel is built for head dims 32 and 64)
+    const size_t res_bytes = (size_t)ceil_div(L, 64) * 64 * DH * 4;   // K + V^T of one (batch, head)
+    if (g_attn_resident && res_bytes <= 128 * 1024 && L >= 128) {
+#ifdef MH_ABLATE
+      // A/B: 16 waves (four per SIMD) when the sequence has a 32-query tile for each of them
+      if (g_attn_resident == 2 && L >= 512) {
+        if (int rc = mh_allow_dynamic_lds((const void*)&attn_res_bf16_kernel<DH, 16>, 128 * 1024)) return rc;
+        mh_prof_note("attn_small kind=res16 B*nh=%d L=%d dh=%d", B * nh, L, DH);
+        MH_LAUNCH((attn_res_bf16_kernel<DH, 16>), dim3(B * nh), dim3(1024), res_bytes, s, q, k, vt, ctx, ld, L, nh, sl2, ctx_panel, g_attn_prof);
+        MH_CHECK_LAUNCH();
+        return MH_OK;
+      }
+#endif
+      if (int rc = mh_allow_dynamic_lds((const void*)&attn_res_bf16_kernel<DH, 8>, 128 * 1024)) return rc;
+      mh_prof_note("attn_small kind=res8 B*nh=%d L=%d dh=%d", B * nh, L, DH);
+      MH_LAUNCH((attn_res_bf16_kernel<DH, 8>), dim3(B * nh), dim3(512), res_bytes, s, q, k, vt, ctx, ld, L, nh, sl2, ctx_panel, g_attn_prof);
+      MH_CHECK_LAUNCH();
+      return MH_OK;
     }
-    // 16 waves (four per SIMD) when the sequence has a 32-query tile for each of them
-    mh_prof_note("attn_small kind=%s B*nh=%d L=%d dh=%d", g_attn_resident == 2 && L >= 512 ? "res16" : "res8", B * nh, L, DH);
-    if (g_attn_resident == 2 && L >= 512)
-      MH_LAUNCH((attn_res_bf16_kernel<DH, 16>), dim3(B * nh), dim3(1024), res_bytes, s, q, k, vt, ctx, ld, L, nh,
-                scale * 1.4426950408889634f, ctx_panel, g_attn_prof);
-    else
-      MH_LAUNCH((attn_res_bf16_kernel<DH, 8>), dim3(B * nh), dim3(512), res_bytes, s, q, k, vt, ctx, ld, L, nh,
-                scale * 1.4426950408889634f, ctx_panel, g_attn_prof);
-    MH_CHECK_LAUNCH();
-    return MH_OK;
   }
   dim3 grid(ceil_div(L, 128), B * nh), block(256);
   mh_prof_note("attn_small kind=tiled B*nh=%d L=%d dh=%d", B * nh, L, DH);
-  MH_LAUNCH((attn_bf16_kernel<DH>), grid, block, 0, s, q, k, vt, ctx, ld, L, nh,
-                     scale * 1.4426950408889634f, ctx_panel);
+  MH_LAUNCH((attn_bf16_kernel<DH>), grid, block, 0, s, q, k, vt, ctx, ld, L, nh, sl2, ctx_panel);
   MH_CHECK_LAUNCH();
   return MH_OK;
 }
 
 }  // namespace
-
-namespace { MH_KNOB(int, g_attn_stream, 1); }
-#ifdef MH_ABLATE
-extern "C" int mh_attention_set_stream(int on) {
-  g_attn_stream = on < 0 ? 0 : (on > 10 ? 10 : on);
-  return MH_OK;
-}
-#endif
-extern "C" int mh_attention_stream_enabled(void) { return g_attn_stream; }
-
-extern "C" int mh_attention_stream_supported(int L, int dh) { return L >= 512 && L % 16 == 0 && (dh == 32 || dh == 64); }
-
-extern "C" int mh_attention_stream_fwd_lse(const void* q, const void* k, const void* vt_perm, void* ctx, int64_t ld_ctx, int ctx_panel,
-                                           int B, int L, int nh, int dh, float scale, float* lse2, mh_stream_t stream);
-extern "C" int mh_attention_stream_fwd_ex(const void* q, const void* k, const void* vt_perm, void* ctx, int64_t ld_ctx, int ctx_panel,
-                                          int B, int L, int nh, int dh, float scale, float* lse2, int64_t qk_batch_stride,
-                                          int64_t qk_head_stride, int64_t qk_row_stride, mh_stream_t stream);
-
-extern "C" int mh_attention_stream_fwd(const void* q, const void* k, const void* vt_perm, void* ctx, int64_t ld_ctx, int ctx_panel,
-                                       int B, int L, int nh, int dh, float scale, mh_stream_t stream) {
-  return mh_attention_stream_fwd_lse(q, k, vt_perm, ctx, ld_ctx, ctx_panel, B, L, nh, dh, scale, nullptr, stream);
-}
-
-extern "C" int mh_attention_stream_fwd_lse(const void* q, const void* k, const void* vt_perm, void* ctx, int64_t ld_ctx, int ctx_panel,
-                                           int B, int L, int nh, int dh, float scale, float* lse2, mh_stream_t stream) {
-  return mh_attention_stream_fwd_ex(q, k, vt_perm, ctx, ld_ctx, ctx_panel, B, L, nh, dh, scale, lse2, (int64_t)nh * L * dh, (int64_t)L * dh, dh,
-                                    stream);
-}
-
-int mh_drop_args(const mh_dropout* d, DropArgs* out);
-extern "C" int mh_attention_stream_fwd_drop(const void* q, const void* k, const void* vt_perm, void* ctx, int64_t ld_ctx, int ctx_panel,
-                                            int B, int L, int nh, int dh, float scale, float* lse2, int64_t qsB, int64_t qsH,
-                                            int64_t qld, const mh_dropout* drop, uint32_t* keep_bits, int bits_in, mh_stream_t stream);
-
-extern "C" int mh_attention_stream_fwd_ex(const void* q, const void* k, const void* vt_perm, void* ctx, int64_t ld_ctx, int ctx_panel,
-                                          int B, int L, int nh, int dh, float scale, float* lse2, int64_t qsB, int64_t qsH,
-                                          int64_t qld, mh_stream_t stream) {
-  return mh_attention_stream_fwd_drop(q, k, vt_perm, ctx, ld_ctx, ctx_panel, B, L, nh, dh, scale, lse2, qsB, qsH, qld, nullptr, nullptr, 0, stream);
-}
-
-// The streaming forward with attention-probability dropout: drop->p > 0 needs `keep_bits` (mh_dropout_bits_words(B nh, L) words):
-// written by the kernel (bits_in = 0: Philox, the same bits mh_dropout_bits produces) or read from it (bits_in = 1).
-namespace {
-int stream_fwd_impl(const void* q, const void* k, const void* vt_perm, void* ctx, int64_t ld_ctx, int ctx_panel, int B, int L, int nh, int dh,
-                    float scale, float* lse2, int64_t qsB, int64_t qsH, int64_t qld, const mh_dropout* drop, uint32_t* keep_bits, int bits_in,
-                    bool pre, mh_stream_t stream);
-}
-// the pre-scaled form is built for whole 256-key stages only (the key-bound variant of it spills)
-extern "C" int mh_attention_stream_prescaled_supported(int L, int dh) { return mh_attention_stream_supported(L, dh) && L % 256 == 0; }
-extern "C" int mh_attention_stream_fwd_drop(const void* q, const void* k, const void* vt_perm, void* ctx, int64_t ld_ctx, int ctx_panel,
-                                            int B, int L, int nh, int dh, float scale, float* lse2, int64_t qsB, int64_t qsH,
-                                            int64_t qld, const mh_dropout* drop, uint32_t* keep_bits, int bits_in, mh_stream_t stream) {
-  return stream_fwd_impl(q, k, vt_perm, ctx, ld_ctx, ctx_panel, B, L, nh, dh, scale, lse2, qsB, qsH, qld, drop, keep_bits, bits_in, false, stream);
-}
-// The same forward for queries that carry scale x log2(e) already (mh_gemm_qkv_vtperm_qs): q [B, nh, L, dh]; no dropout
-extern "C" int mh_attention_stream_fwd_prescaled(const void* q, const void* k, const void* vt_perm, void* ctx, int64_t ld_ctx, int ctx_panel,
-                                                 int B, int L, int nh, int dh, mh_stream_t stream) {
-  return stream_fwd_impl(q, k, vt_perm, ctx, ld_ctx, ctx_panel, B, L, nh, dh, 1.0f, nullptr, (int64_t)nh * L * dh, (int64_t)L * dh, dh, nullptr,
-                         nullptr, 0, true, stream);
-}
-namespace {
-// which instantiation a launch is, for the launch note (every instantiation has the same function type, so the pointer cannot tell):
-// of<...>() takes the kernel's template arguments with the kernel's defaults
-struct StreamVariant {
-  int nw, sk, dropv, full, kvnt, pre;
-  template <int DH, int NW = 16, int SK = 256, int DROP = 0, bool FULL = false, bool KVNT = false, bool PRE = false, int ABL = 0, int PRIO = 0>
-  static constexpr StreamVariant of() { return {NW, SK, DROP, FULL, KVNT, PRE}; }
-};
-#define MH_STREAM_GO(bytes, ...) go(&attn_stream_bf16_kernel<__VA_ARGS__>, bytes, StreamVariant::of<__VA_ARGS__>())
-int stream_fwd_impl(const void* q, const void* k, const void* vt_perm, void* ctx, int64_t ld_ctx, int ctx_panel, int B, int L, int nh, int dh,
-                    float scale, float* lse2, int64_t qsB, int64_t qsH, int64_t qld, const mh_dropout* drop, uint32_t* keep_bits, int bits_in,
-                    bool pre, mh_stream_t stream) {
-  DropArgs da;
-  int rcd = mh_drop_args(drop, &da);
-  if (rcd) return rcd;
-  const bool dropping = da.thr != 0;
-  MH_CHECK_ARG(!dropping || keep_bits, "attention_stream: dropout needs the keep_bits tensor");
-  MH_CHECK_ARG(!(pre && dropping), "attention_stream: the pre-scaled form has no dropout variant");
-  MH_CHECK_ARG(qld % 8 == 0 && qsH % 8 == 0 && qsB % 8 == 0 && qld >= dh, "attention_stream: q/k strides must be multiples of 8 elements");
-  MH_CHECK_ARG(q && k && vt_perm && ctx, "attention_stream: null pointer");
-  MH_CHECK_ARG(B > 0 && nh > 0 && mh_attention_stream_supported(L, dh),
-               "attention_stream: needs seq_len %% 16 == 0, seq_len >= 512 and head dim 32 or 64 (got L=%d dh=%d)", L, dh);
-  MH_CHECK_ARG(ctx_panel || ld_ctx % 4 == 0, "attention_stream: ld_ctx must be a multiple of 4");
-  hipStream_t s = (hipStream_t)stream;
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-  const int nbh = B * nh;
-  const float sl2 = scale * 1.4426950408889634f;
-  const bf16 *Q = (const bf16*)q, *K = (const bf16*)k, *V = (const bf16*)vt_perm;
-  // 8 waves x 128-key stages: half a CU per block.  The dropout variant always runs there: its mask generation needs ~30
-  // registers more than the 128 a 16-wave block leaves each wave (the 16-wave build spilled 82 dwords per lane: 3.5x slower)
-  // the in-kernel generator runs on the 8-wave geometry (its Philox state does not fit the 128 registers of a 16-wave block without
-  // spilling 25 dwords per lane; mode 3 = A/B: generator on 16 waves); the bit reader fits 16 waves
-  // modes 5 / 6 (A/B): the 8-wave geometry on ONE block per CU (each block then walks two half-items back to back, the second one's
-  // first stage and queries arriving under the first one's tiles, and half of the CU's LDS and registers stay free for a block of the
-  // other graph branch's kernel); 6: the 16-wave geometry with as many blocks as half the CUs (two items per block)
-  const bool small = !pre && (g_attn_stream == 2 || g_attn_stream == 5 || (dropping && !bits_in && g_attn_stream != 3));
-  const int qper = small ? 256 : 512, nitems = nbh * ((L + qper - 1) / qper);
-  const int slots = g_attn_stream == 5 ? cus : (g_attn_stream == 6 ? cus / 2 : (small ? 2 * cus : cus));
-  const dim3 grid((unsigned)(nitems < slots ? nitems : slots)), block(small ? 512 : 1024);
-  auto go = [&](auto kern, int bytes, StreamVariant v) -> int {
-    // all instantiations share one function-pointer type, so this lambda body exists once: the attribute is tracked per kernel
-    static std::set<std::pair<int, const void*>> attr_done;   // (device, kernel); guarded: the library may be called from several host threads
-    static std::mutex attr_mu;
-    {
-      std::lock_guard<std::mutex> lock(attr_mu);
-      if (attr_done.insert({mh_current_device(), reinterpret_cast<const void*>(kern)}).second)
-        MH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    }
-    mh_prof_note("attn_stream B*nh=%d L=%d dh=%d drop=%d nw=%d sk=%d dropv=%d full=%d kvnt=%d pre=%d items=%d", nbh, L, dh, (int)dropping, v.nw, v.sk,
-                 v.dropv, v.full, v.kvnt, v.pre, nitems);
-    MH_LAUNCH(kern, grid, block, bytes, s, Q, K, V, (bf16*)ctx, ld_ctx, L, nh, nbh, sl2, ctx_panel, lse2, qsB, qsH, qld, da, keep_bits, bits_in);
-    return MH_OK;
-  };
-  if (g_attn_stream == 7 && !pre && !dropping && !lse2 && dh == 64 && L % 512 == 0 && (ctx_panel || (ld_ctx % 8 == 0 && (reinterpret_cast<uintptr_t>(ctx) & 15) == 0))) {
-    // A/B: 64 queries per wave (8 waves, two per SIMD): half the LDS fragment reads per (batch, head)
-    const int items2 = nbh * (L / 512);
-    const dim3 grid2((unsigned)(items2 < cus ? items2 : cus));
-    static std::set<std::pair<int, const void*>> attr2;
-    static std::mutex attr2_mu;
-    const bool kvnt = L <= 512;
-    const void* kp = kvnt ? reinterpret_cast<const void*>(&attn_stream2_kernel<true>) : reinterpret_cast<const void*>(&attn_stream2_kernel<false>);
-    {
-      std::lock_guard<std::mutex> lock(attr2_mu);
-      if (attr2.insert({mh_current_device(), kp}).second) MH_HIP(hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 256 * 64 * 2));
-    }
-    mh_prof_note("attn_stream2 B*nh=%d L=%d dh=%d", nbh, L, dh);
-    if (kvnt) MH_LAUNCH((attn_stream2_kernel<true>), grid2, dim3(512), 4 * 256 * 64 * 2, s, Q, K, V, (bf16*)ctx, ld_ctx, L, nh, nbh, sl2, ctx_panel, qsB, qsH, qld);
-    else MH_LAUNCH((attn_stream2_kernel<false>), grid2, dim3(512), 4 * 256 * 64 * 2, s, Q, K, V, (bf16*)ctx, ld_ctx, L, nh, nbh, sl2, ctx_panel, qsB, qsH, qld);
-    MH_CHECK_LAUNCH();
-    return MH_OK;
-  }
-  int rc;
-  const bool full = L % 256 == 0 && g_attn_stream != 4;   // (mode 4 = A/B: the key-bound build on every length)
-  if (dropping && bits_in && small) {   // (mode 2: the bit reader on the 8-wave geometry too)
-    rc = dh == 64 ? MH_STREAM_GO(4 * 128 * 64 * 2, 64, 8, 128, 2) : MH_STREAM_GO(4 * 256 * 32 * 2, 32, 8, 256, 2);
-  } else if (dropping && bits_in && full && dh == 64) {   // (round 6: the reader without the per-score bound compares where no tile is partial - config 5's seq_len 1024)
-    rc = MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 2, true);
-  } else if (dropping && bits_in) {
-    rc = dh == 64 ? MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 2) : MH_STREAM_GO(4 * 256 * 32 * 2, 32, 16, 256, 2);
-  } else if (dropping && !small) rc = dh == 64 ? MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 1) : MH_STREAM_GO(4 * 256 * 32 * 2, 32, 16, 256, 1);
-  else if (dropping) rc = dh == 64 ? MH_STREAM_GO(4 * 128 * 64 * 2, 64, 8, 128, 1) : MH_STREAM_GO(4 * 256 * 32 * 2, 32, 8, 256, 1);
-  else if (pre) {
-    // pre-scaled queries (the sampler's forward): 16 waves, the same FULL / KVNT choices as below
-    MH_CHECK_ARG(mh_attention_stream_prescaled_supported(L, dh), "attention_stream(pre-scaled): seq_len %d must be a multiple of 256", L);
-    if (L <= 512) rc = dh == 64 ? MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, true) : MH_STREAM_GO(4 * 256 * 32 * 2, 32, 16, 256, 0, true, true, true);
-    else rc = dh == 64 ? MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, false, true) : MH_STREAM_GO(4 * 256 * 32 * 2, 32, 16, 256, 0, true, false, true);
-  }
-  else if (g_attn_abl && full && !small && L <= qper && dh == 64) {
-    switch (g_attn_abl) {
-      case 1: rc = MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, false, 1); break;
-      case 2: rc = MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, false, 2); break;
-      case 4: rc = MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, false, 4); break;
-      case 6: rc = MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, false, 6); break;
-      case 7: rc = MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, false, 7); break;
-      case 8: rc = MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, false, 8); break;
-      case 16: rc = MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, false, 16); break;
-      case 24: rc = MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, false, 24); break;
-      case 31: rc = MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, false, 31); break;
-      case 63: rc = MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, false, 63); break;
-      case 95: rc = MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, false, 95); break;
-      case 127: rc = MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, false, 127); break;
-      case 32: rc = MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, false, 32); break;
-      case 128: rc = MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, false, 128); break;   // phase profile into keep_bits (tools/attn_bench.py --prof)
-      default: mh_set_error("attention_stream: ablation %d not built (1 2 4 6 7 8 16 24 31)", g_attn_abl); return MH_ERR_UNSUPPORTED;
-    }
-  }
-#ifdef MH_ABLATE
-  // A/B: 8 = 128-key stages on the 16-wave block (first MFMA after 32 KB instead of 64 KB have landed, 64 KB of LDS per block), 9 = static
-  // priority for the younger half of the waves, 10 = both
-  else if (g_attn_stream >= 8 && full && !small && L <= qper && dh == 64)
-    rc = g_attn_stream == 8 ? MH_STREAM_GO(4 * 128 * 64 * 2, 64, 16, 128, 0, true, true)
-       : g_attn_stream == 9 ? MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true, false, 0, 1)
-                            : MH_STREAM_GO(4 * 128 * 64 * 2, 64, 16, 128, 0, true, true, false, 0, 1);
-#endif
-  else if (full && !small && L <= qper)   // one block streams a (batch, head)'s K / V once: nt policy
-    rc = dh == 64 ? MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true, true) : MH_STREAM_GO(4 * 256 * 32 * 2, 32, 16, 256, 0, true, true);
-  else if (full && dh == 64) rc = small ? MH_STREAM_GO(4 * 128 * 64 * 2, 64, 8, 128, 0, true) : MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256, 0, true);
-  else if (full) rc = small ? MH_STREAM_GO(4 * 256 * 32 * 2, 32, 8, 256, 0, true) : MH_STREAM_GO(4 * 256 * 32 * 2, 32, 16, 256, 0, true);
-  else if (dh == 64) rc = small ? MH_STREAM_GO(4 * 128 * 64 * 2, 64, 8, 128) : MH_STREAM_GO(4 * 256 * 64 * 2, 64, 16, 256);
-  else rc = small ? MH_STREAM_GO(4 * 256 * 32 * 2, 32, 8, 256) : MH_STREAM_GO(4 * 256 * 32 * 2, 32, 16, 256);
-  if (rc) return rc;
-  MH_CHECK_LAUNCH();
-  return MH_OK;
-}
-#undef MH_STREAM_GO
-}  // namespace
-
-#ifdef MH_ABLATE
-extern "C" int mh_attention_set_ablation(int bits) {
-  g_attn_abl = bits;
-  return MH_OK;
-}
-#endif
 
 #ifdef MH_ABLATE
 extern "C" int mh_attention_set_profile(void* stamps) {
   g_attn_prof = reinterpret_cast<unsigned long long*>(stamps);
   return MH_OK;
 }
-#endif
-
-#ifdef MH_ABLATE
 extern "C" int mh_attention_set_variant(int resident) {
   g_attn_resident = resident < 0 ? 0 : (resident > 2 ? 2 : resident);
   return MH_OK;
 }
 #endif
-
-extern "C" int mh_attention_fwd_ex(const void* q, const void* k, const void* vt, void* ctx, int64_t ld_ctx,
-                                   int ctx_panel, int B, int L, int nh, int dh, float scale, int dtype, mh_stream_t stream);
-
-extern "C" int mh_attention_fwd(const void* q, const void* k, const void* vt, void* ctx, int64_t ld_ctx, int B,
-                                int L, int nh, int dh, float scale, int dtype, mh_stream_t stream) {
-  return mh_attention_fwd_ex(q, k, vt, ctx, ld_ctx, 0, B, L, nh, dh, scale, dtype, stream);
-}
 
 extern "C" int mh_attention_fwd_ex(const void* q, const void* k, const void* vt, void* ctx, int64_t ld_ctx,
                                    int ctx_panel, int B, int L, int nh, int dh, float scale, int dtype, mh_stream_t stream) {
@@ -1396,4 +631,9 @@ extern "C" int mh_attention_fwd_ex(const void* q, const void* k, const void* vt,
   }
   mh_set_error("attention: unknown dtype %d", dtype);
   return MH_ERR_INVALID;
+}
+
+extern "C" int mh_attention_fwd(const void* q, const void* k, const void* vt, void* ctx, int64_t ld_ctx, int B,
+                                int L, int nh, int dh, float scale, int dtype, mh_stream_t stream) {
+  return mh_attention_fwd_ex(q, k, vt, ctx, ld_ctx, 0, B, L, nh, dh, scale, dtype, stream);
 }

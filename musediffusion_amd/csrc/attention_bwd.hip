@@ -1,5 +1,5 @@
 // Fused attention backward (bf16 MFMA, gfx950) for training_losses (models/diffusion.py:594-699 -> HF
-// BertSelfAttention backward).  Two streaming kernels in the mould of attn_stream_bf16_kernel (attention.hip):
+// BertSelfAttention backward).  Two streaming kernels in the mould of attn_stream_bf16_kernel (attn_stream.h):
 // persistent 8-wave blocks, operands copied into LDS by LDS-DMA in 128-row stages, double-buffered, the score
 // matrix never leaves registers.  P is re-created from the forward's log-sum-exp: P[q][k] = exp2(s c - lse2[q]).
 //
@@ -518,19 +518,13 @@ __global__ void attn_bwd_rowdot_kernel(const bf16* __restrict__ dctx, const bf16
 }
 
 template <int DH, bool DROP, bool FULL>
-int launch_bwd(const bf16* q, const bf16* k, const bf16* v, const bf16* qT, const bf16* kT, const bf16* dO, const bf16* dOT, const bf16* o,
+int launch_bwd(const bf16* q, const bf16* k, const bf16* v, const bf16* dO, const bf16* o,
                const float* lse2, float* Dv, bf16* dq, bf16* dk, bf16* dv, int64_t ld, int B, int L, int nh, float scale,
                RowLayout lqkv, RowLayout ldo, const uint32_t* keep_bits, float rscale, hipStream_t s, int o_panel = 0, int64_t o_ld = 0, int d_panel = 0) {
   constexpr int ST = SKB * DH * 2;
   constexpr int bytes_dq = 2 * 2 * ST + (DROP && FULL ? 2 * 8 * (SKB / 64) * 256 : 0), bytes_dkv = 2 * (2 * ST + 2 * SKB * 4 + (DROP && FULL ? (SKB / 32) * 1024 : 0));
-  (void)qT; (void)kT; (void)dOT;   // (the transposed copies of the round-2 interface: no longer read)
-  static bool attr_set[MH_MAX_DEVICES] = {};   // per device: hipFuncSetAttribute acts on the current device's copy of the kernel
-  const int adev = mh_current_device();
-  if (!attr_set[adev]) {
-    MH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dq_kernel<DH, DROP, FULL>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes_dq));
-    MH_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkv_kernel<DH, DROP, FULL>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes_dkv));
-    attr_set[adev] = true;
-  }
+  if (int rc = mh_allow_dynamic_lds((const void*)&attn_bwd_dq_kernel<DH, DROP, FULL>, bytes_dq)) return rc;
+  if (int rc = mh_allow_dynamic_lds((const void*)&attn_bwd_dkv_kernel<DH, DROP, FULL>, bytes_dkv)) return rc;
   int dev = 0, cus = 256;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
   const int nbh = B * nh, nitems = nbh * ((L + 255) / 256);
@@ -561,40 +555,37 @@ extern "C" int mh_attention_bwd_rowdot(const void* dctx, const void* ctx, int64_
   return MH_OK;
 }
 
+// The backward with the layouts of O and of the three outputs chosen by the caller: o_panel / d_panel != 0: K32 panels [H / 32][o_ld | ld_d rows][32]
+// of the token-major tensors (dq / dk / dv then point at the first panel of their column block); dO (and, row-major, O) in the os* row layout.
+// `keep_bits` is the bit tensor the forward wrote (or was given) when it dropped probabilities with rate drop_p; null / drop_p == 0: no dropout.
 extern "C" int mh_attention_stream_bwd_layout(const void* q, const void* k, const void* v, const void* dO, const void* o, int o_panel, int64_t o_ld,
                                               const float* lse2, float* D, void* dq, void* dk, void* dv, int64_t ld_d, int d_panel, int B, int L,
                                               int nh, int dh, float scale, int64_t qsB, int64_t qsH, int64_t qld, int64_t osB, int64_t osH,
-                                              int64_t old_, const uint32_t* keep_bits, float drop_p, mh_stream_t stream);
-extern "C" int mh_attention_stream_bwd_ex(const void* q, const void* k, const void* v, const void* qT_perm, const void* kT_perm,
-                                          const void* dO, const void* dOT_perm, const void* o, const float* lse2, float* D, void* dq, void* dk,
-                                          void* dv, int64_t ld_d, int B, int L, int nh, int dh, float scale, int64_t qkv_batch_stride,
-                                          int64_t qkv_head_stride, int64_t qkv_row_stride, int64_t do_batch_stride,
-                                          int64_t do_head_stride, int64_t do_row_stride, mh_stream_t stream);
-
-extern "C" int mh_attention_stream_bwd(const void* q, const void* k, const void* v, const void* qT_perm, const void* kT_perm,
-                                       const void* dO, const void* dOT_perm, const void* o, const float* lse2, float* D, void* dq, void* dk,
-                                       void* dv, int64_t ld_d, int B, int L, int nh, int dh, float scale, mh_stream_t stream) {
-  const int64_t sB = (int64_t)nh * L * dh, sH = (int64_t)L * dh;
-  return mh_attention_stream_bwd_ex(q, k, v, qT_perm, kT_perm, dO, dOT_perm, o, lse2, D, dq, dk, dv, ld_d, B, L, nh, dh, scale, sB, sH, dh,
-                                    sB, sH, dh, stream);
+                                              int64_t old_, const uint32_t* keep_bits, float drop_p, mh_stream_t stream) {
+  MH_CHECK_ARG(!o_panel || o_ld >= (int64_t)B * L, "attention_stream_bwd: o_ld must cover the B L token rows");
+  MH_CHECK_ARG(!d_panel || ld_d >= (int64_t)B * L, "attention_stream_bwd: ld_d must cover the B L token rows");
+  MH_CHECK_ARG(qsB % 8 == 0 && qsH % 8 == 0 && qld % 8 == 0 && osB % 8 == 0 && osH % 8 == 0 && old_ % 8 == 0 && qld >= dh && old_ >= dh,
+               "attention_stream_bwd: row strides must be multiples of 8 elements");
+  const RowLayout lqkv{qsB, qsH, qld}, ldo{osB, osH, old_};
+  MH_CHECK_ARG(q && k && v && dO && o && lse2 && D && dq && dk && dv, "attention_stream_bwd: null pointer");
+  MH_CHECK_ARG(B > 0 && nh > 0 && mh_attention_stream_bwd_supported(L, dh),
+               "attention_stream_bwd: needs seq_len %% 16 == 0, seq_len >= 512 and head dim 32 or 64 (got L=%d dh=%d)", L, dh);
+  MH_CHECK_ARG(ld_d % 4 == 0, "attention_stream_bwd: ld_d must be a multiple of 4");
+  MH_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || keep_bits), "attention_stream_bwd: dropout needs keep_bits and p in [0, 1)");   // (p == 0 with keep_bits: the MH_BWD_PROF debug build's output buffer)
+  hipStream_t s = (hipStream_t)stream;
+  const float rs = 1.0f / (1.0f - drop_p);
+#define MH_BWD_ARGS (const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)dO, (const bf16*)o, lse2, D, (bf16*)dq, (bf16*)dk, (bf16*)dv, ld_d, B, L, \
+                    nh, scale, lqkv, ldo, keep_bits, rs, s, o_panel, o_ld, d_panel
+  if (L % 256 == 0 && mh_attention_stream_enabled() != 4) {   // (mode 4 = A/B: the bound-checking build on every length)
+    if (drop_p > 0.f) return dh == 64 ? launch_bwd<64, true, true>(MH_BWD_ARGS) : launch_bwd<32, true, true>(MH_BWD_ARGS);
+    return dh == 64 ? launch_bwd<64, false, true>(MH_BWD_ARGS) : launch_bwd<32, false, true>(MH_BWD_ARGS);
+  }
+  if (drop_p > 0.f) return dh == 64 ? launch_bwd<64, true, false>(MH_BWD_ARGS) : launch_bwd<32, true, false>(MH_BWD_ARGS);
+  return dh == 64 ? launch_bwd<64, false, false>(MH_BWD_ARGS) : launch_bwd<32, false, false>(MH_BWD_ARGS);
+#undef MH_BWD_ARGS
 }
 
-extern "C" int mh_attention_stream_bwd_drop(const void* q, const void* k, const void* v, const void* qT_perm, const void* kT_perm,
-                                            const void* dO, const void* dOT_perm, const void* o, const float* lse2, float* D, void* dq, void* dk,
-                                            void* dv, int64_t ld_d, int B, int L, int nh, int dh, float scale, int64_t qsB, int64_t qsH,
-                                            int64_t qld, int64_t osB, int64_t osH, int64_t old_, const uint32_t* keep_bits, float drop_p,
-                                            mh_stream_t stream);
-
-extern "C" int mh_attention_stream_bwd_ex(const void* q, const void* k, const void* v, const void* qT_perm, const void* kT_perm,
-                                          const void* dO, const void* dOT_perm, const void* o, const float* lse2, float* D, void* dq, void* dk,
-                                          void* dv, int64_t ld_d, int B, int L, int nh, int dh, float scale, int64_t qsB, int64_t qsH,
-                                          int64_t qld, int64_t osB, int64_t osH, int64_t old_, mh_stream_t stream) {
-  return mh_attention_stream_bwd_drop(q, k, v, qT_perm, kT_perm, dO, dOT_perm, o, lse2, D, dq, dk, dv, ld_d, B, L, nh, dh, scale, qsB, qsH, qld,
-                                      osB, osH, old_, nullptr, 0.f, stream);
-}
-
-// Backward of the streaming attention whose forward dropped probabilities with rate drop_p: `keep_bits` is the bit tensor that
-// forward wrote (or was given); null / drop_p == 0: no dropout.
+// The row-major forms.  qT_perm, kT_perm, dOT_perm (the transposed copies of the round-2 interface) are no longer read and may be null.
 extern "C" int mh_attention_stream_bwd_drop(const void* q, const void* k, const void* v, const void* qT_perm, const void* kT_perm,
                                             const void* dO, const void* dOT_perm, const void* o, const float* lse2, float* D, void* dq, void* dk,
                                             void* dv, int64_t ld_d, int B, int L, int nh, int dh, float scale, int64_t qsB, int64_t qsH,
@@ -605,33 +596,18 @@ extern "C" int mh_attention_stream_bwd_drop(const void* q, const void* k, const 
                                         drop_p, stream);
 }
 
-// The same with the layouts of O and of the three outputs chosen by the caller: o_panel / d_panel != 0: K32 panels [H / 32][o_ld | ld_d rows][32]
-// of the token-major tensors (dq / dk / dv then point at the first panel of their column block); dO (and, row-major, O) in the os* row layout.
-extern "C" int mh_attention_stream_bwd_layout(const void* q, const void* k, const void* v, const void* dO, const void* o, int o_panel, int64_t o_ld,
-                                              const float* lse2, float* D, void* dq, void* dk, void* dv, int64_t ld_d, int d_panel, int B, int L,
-                                              int nh, int dh, float scale, int64_t qsB, int64_t qsH, int64_t qld, int64_t osB, int64_t osH,
-                                              int64_t old_, const uint32_t* keep_bits, float drop_p, mh_stream_t stream) {
-  const void* qT_perm = nullptr; const void* kT_perm = nullptr; const void* dOT_perm = nullptr;
-  MH_CHECK_ARG(!o_panel || o_ld >= (int64_t)B * L, "attention_stream_bwd: o_ld must cover the B L token rows");
-  MH_CHECK_ARG(!d_panel || ld_d >= (int64_t)B * L, "attention_stream_bwd: ld_d must cover the B L token rows");
-  MH_CHECK_ARG(qsB % 8 == 0 && qsH % 8 == 0 && qld % 8 == 0 && osB % 8 == 0 && osH % 8 == 0 && old_ % 8 == 0 && qld >= dh && old_ >= dh,
-               "attention_stream_bwd: row strides must be multiples of 8 elements");
-  const RowLayout lqkv{qsB, qsH, qld}, ldo{osB, osH, old_};
-  MH_CHECK_ARG(q && k && v && dO && o && lse2 && D && dq && dk && dv, "attention_stream_bwd: null pointer");   // (qT_perm, kT_perm, dOT_perm: unused, may be null)
-  MH_CHECK_ARG(B > 0 && nh > 0 && mh_attention_stream_bwd_supported(L, dh),
-               "attention_stream_bwd: needs seq_len %% 16 == 0, seq_len >= 512 and head dim 32 or 64 (got L=%d dh=%d)", L, dh);
-  MH_CHECK_ARG(ld_d % 4 == 0, "attention_stream_bwd: ld_d must be a multiple of 4");
-  MH_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || keep_bits), "attention_stream_bwd: dropout needs keep_bits and p in [0, 1)");   // (p == 0 with keep_bits: the MH_BWD_PROF debug build's output buffer)
-  hipStream_t s = (hipStream_t)stream;
-  const float rs = 1.0f / (1.0f - drop_p);
-#define MH_BWD_ARGS (const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)qT_perm, (const bf16*)kT_perm, (const bf16*)dO, \
-                    (const bf16*)dOT_perm, (const bf16*)o, lse2, D, (bf16*)dq, (bf16*)dk, (bf16*)dv, ld_d, B, L, nh, scale, lqkv, ldo, keep_bits, rs, s, \
-                    o_panel, o_ld, d_panel
-  if (L % 256 == 0 && mh_attention_stream_enabled() != 4) {   // (mode 4 = A/B: the bound-checking build on every length)
-    if (drop_p > 0.f) return dh == 64 ? launch_bwd<64, true, true>(MH_BWD_ARGS) : launch_bwd<32, true, true>(MH_BWD_ARGS);
-    return dh == 64 ? launch_bwd<64, false, true>(MH_BWD_ARGS) : launch_bwd<32, false, true>(MH_BWD_ARGS);
-  }
-  if (drop_p > 0.f) return dh == 64 ? launch_bwd<64, true, false>(MH_BWD_ARGS) : launch_bwd<32, true, false>(MH_BWD_ARGS);
-  return dh == 64 ? launch_bwd<64, false, false>(MH_BWD_ARGS) : launch_bwd<32, false, false>(MH_BWD_ARGS);
-#undef MH_BWD_ARGS
+extern "C" int mh_attention_stream_bwd_ex(const void* q, const void* k, const void* v, const void* qT_perm, const void* kT_perm,
+                                          const void* dO, const void* dOT_perm, const void* o, const float* lse2, float* D, void* dq, void* dk,
+                                          void* dv, int64_t ld_d, int B, int L, int nh, int dh, float scale, int64_t qsB, int64_t qsH,
+                                          int64_t qld, int64_t osB, int64_t osH, int64_t old_, mh_stream_t stream) {
+  return mh_attention_stream_bwd_drop(q, k, v, qT_perm, kT_perm, dO, dOT_perm, o, lse2, D, dq, dk, dv, ld_d, B, L, nh, dh, scale, qsB, qsH, qld,
+                                      osB, osH, old_, nullptr, 0.f, stream);
+}
+
+extern "C" int mh_attention_stream_bwd(const void* q, const void* k, const void* v, const void* qT_perm, const void* kT_perm,
+                                       const void* dO, const void* dOT_perm, const void* o, const float* lse2, float* D, void* dq, void* dk,
+                                       void* dv, int64_t ld_d, int B, int L, int nh, int dh, float scale, mh_stream_t stream) {
+  const int64_t sB = (int64_t)nh * L * dh, sH = (int64_t)L * dh;
+  return mh_attention_stream_bwd_ex(q, k, v, qT_perm, kT_perm, dO, dOT_perm, o, lse2, D, dq, dk, dv, ld_d, B, L, nh, dh, scale, sB, sH, dh,
+                                    sB, sH, dh, stream);
 }

@@ -3,6 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <mutex>
+#include <set>
+#include <utility>
+
 #include "../../include/musehip.h"
 
 // A/B switches, ablation knobs and diagnostics (include/musehip_dbg.h) exist only in the debug library (-DMH_ABLATE ->
@@ -10,9 +14,8 @@
 // constant holding the default and the setters are not compiled.  A constant-false `if` does NOT keep a kernel out of the library (the
 // launch in its body still instantiates the template), so a launch site that only a knob away from its default can reach stands inside
 // #ifdef MH_ABLATE: the product library does not contain the kernel at all.  DESIGN.md, "GEMM sources", lists what that removes and
-// how the product's kernel list is compared against the debug library's.
-// per-device bookkeeping of hipFuncSetAttribute (it acts on the CURRENT device's copy of a kernel): the library may serve several
-// devices from one process
+// how the product's kernel list is compared against the debug library's; "Attention sources" does the same for the attention family.
+// per-device bookkeeping: the library may serve several devices from one process
 constexpr int MH_MAX_DEVICES = 64;
 static inline int mh_current_device() {
   int dev = 0;
@@ -75,6 +78,19 @@ void mh_prof_note(const char* fmt, ...);     // free-form detail attached to the
       return MH_ERR_HIP;                                         \
     }                                                            \
   } while (0)
+
+// Allow `kernel` `bytes` of dynamic LDS on the current device, once per (device, kernel): hipFuncSetAttribute acts on the CURRENT device's
+// copy of a kernel, and the library may be called from several host threads.  Returns MH_OK or MH_ERR_HIP.
+static inline int mh_allow_dynamic_lds(const void* kernel, size_t bytes) {
+  static std::mutex mu;
+  static std::set<std::pair<int, const void*>> done;
+  const std::pair<int, const void*> key(mh_current_device(), kernel);
+  std::lock_guard<std::mutex> lock(mu);
+  if (done.count(key)) return MH_OK;
+  MH_HIP(hipFuncSetAttribute(key.second, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  done.insert(key);
+  return MH_OK;
+}
 
 // ---- scalar conversions.  Plain casts: hipcc emits v_cvt_pk_bf16_f32 (RNE, NaN-preserving).
 __device__ __forceinline__ float to_f32(float v) { return v; }

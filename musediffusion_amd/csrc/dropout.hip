@@ -3,7 +3,7 @@
 //   mh_dropout_fwd         y = x o keep / (1 - p) over a dense [rows, cols] activation: the embedding-LayerNorm site forward,
 //                          and the BACKWARD of every dense site (the mask is re-created from (seed, offset), never stored)
 //   mh_dropout_bits        the attention-probability keep mask as a bit tensor (lane-native layout, common.h drop_word_index),
-//                          exactly the words the fused forward (attention.hip) writes
+//                          exactly the words the fused forward (attn_stream.h) writes
 //   mh_dropout_bits_apply  P o keep / (1 - p) on a materialised [B nh, L, ldp] probability / gradient tensor (fp32 parity mode
 //                          and shapes the streaming kernels do not serve)
 // The Philox counter conventions live in common.h (drop_keep8 / drop_keep_attn).

@@ -2,7 +2,7 @@
 
 * `census_key`: (kernel text, launch note) -> census key of an attention-family launch.  Every instantiation of the streaming forward is
   launched through one function pointer, so the recorder's kernel text is `kern` for all of them: the key is built from the note's
-  `key=value` fields, which name the instantiation (csrc/attention.hip: stream_fwd_impl; csrc/attention_bwd.hip: launch_bwd).
+  `key=value` fields, which name the instantiation (csrc/attention_stream.hip: stream_fwd_impl; csrc/attention_bwd.hip: launch_bwd).
 * `record`: tests/gemm_census.py's recorder for this family -> [(key, note, grid)].
 * `fwd_key` / `bwd_keys`: the keys of a streaming variant, as the matrix and PARITY spell them.
 * `WORKLOADS`: the GEMM census' eager runs plus one forward at the reference's own shape (seq_len 2096: the key-bound forward)."""

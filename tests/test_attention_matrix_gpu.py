@@ -1,5 +1,5 @@
-"""Parity matrix of the streaming attention family: every instantiation the dispatchers can pick in the product build (csrc/attention.hip:
-stream_fwd_impl, 15 forward builds; csrc/attention_bwd.hip: launch_bwd, 8 <DH, DROP, FULL> pairs of kernels) against a float64 reference
+"""Parity matrix of the streaming attention family: every instantiation the dispatchers can pick in the product build (csrc/attention_stream.hip:
+kStreamProduct, 15 forward builds; csrc/attention_bwd.hip: launch_bwd, 8 <DH, DROP, FULL> pairs of kernels) against a float64 reference
 on the CPU (tests/attention_ref.py), EVERY element of EVERY output, at the shapes where a persistent streaming kernel goes wrong:
 
 * ragged (key-bound builds): seq_len 528 / 784 / 2096 - not a multiple of 256 nor of 32 (a 16-row last tile), a last query block in which
