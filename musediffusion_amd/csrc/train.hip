@@ -733,6 +733,7 @@ extern "C" int mh_head_permute(const void* in, void* out, int64_t ld_tok, int B,
   const bool vec_ok = dtype == MH_BF16 && dh % 8 == 0 && ld_tok % 8 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0 &&
                       (reinterpret_cast<uintptr_t>(out) & 15) == 0;
   if (vec_ok && mode <= 1) {
+    mh_prof_note("mode=%d", mode);
     MH_LAUNCH(head_permute8_kernel, dim3(tgrid((int64_t)B * L * nh * (dh / 8))), dim3(TB), 0, s, (const bf16*)in, (bf16*)out, ld_tok, B, L,
               nh, dh / 8, mode);
     MH_CHECK_LAUNCH();
@@ -741,6 +742,7 @@ extern "C" int mh_head_permute(const void* in, void* out, int64_t ld_tok, int B,
   if (vec_ok && mode >= 2 && L % 64 == 0 && (dh == 32 || dh == 64 || dh == 128)) {
     const dim3 grid(L / 64, B * nh);
     const int perm = mode == 4 ? 2 : (mode == 3 ? 1 : 0);
+    mh_prof_note("mode=%d", mode);
     if (dh == 32) MH_LAUNCH((head_transpose_kernel<32>), grid, dim3(256), 0, s, (const bf16*)in, (bf16*)out, ld_tok, L, nh, perm);
     else if (dh == 64) MH_LAUNCH((head_transpose_kernel<64>), grid, dim3(256), 0, s, (const bf16*)in, (bf16*)out, ld_tok, L, nh, perm);
     else MH_LAUNCH((head_transpose_kernel<128>), grid, dim3(256), 0, s, (const bf16*)in, (bf16*)out, ld_tok, L, nh, perm);
@@ -750,8 +752,8 @@ extern "C" int mh_head_permute(const void* in, void* out, int64_t ld_tok, int B,
   MH_CHECK_ARG(mode != 4, "head_permute: mode 4 needs bf16, seq_len %% 64 == 0, head dim 32 / 64 / 128 and 16-byte aligned rows");
   const int grid = tgrid((int64_t)B * L * nh * dh);
   MH_DTYPE_SWITCH(dtype,
-                  MH_LAUNCH((head_permute_kernel<bf16>), dim3(grid), dim3(TB), 0, s, (const bf16*)in, (bf16*)out, ld_tok, B, L, nh, dh, mode),
-                  MH_LAUNCH((head_permute_kernel<float>), dim3(grid), dim3(TB), 0, s, (const float*)in, (float*)out, ld_tok, B, L, nh, dh, mode),
+                  mh_prof_note("mode=%d", mode); MH_LAUNCH((head_permute_kernel<bf16>), dim3(grid), dim3(TB), 0, s, (const bf16*)in, (bf16*)out, ld_tok, B, L, nh, dh, mode),
+                  mh_prof_note("mode=%d", mode); MH_LAUNCH((head_permute_kernel<float>), dim3(grid), dim3(TB), 0, s, (const float*)in, (float*)out, ld_tok, B, L, nh, dh, mode),
                   "head_permute");
   MH_CHECK_LAUNCH();
   return MH_OK;
@@ -763,7 +765,7 @@ extern "C" int mh_col_sum(const void* in, int64_t ld, int64_t rows, int cols, in
                "col_sum: bad arguments");
   hipStream_t s = (hipStream_t)stream;
   const int vec = dtype == MH_BF16 ? 8 : 4;
-  if (cols % vec == 0 && ld % vec == 0 && stride_in % vec == 0) {
+  if (cols % vec == 0 && ld % vec == 0 && stride_in % vec == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0) {
     dim3 grid((cols / vec + 63) / 64, n_partial, batch);
     MH_DTYPE_SWITCH(dtype, MH_LAUNCH((colsum8_partial_kernel<bf16>), grid, dim3(256), 0, s, (const bf16*)in, ld, rows, cols, partial, stride_in),
                     MH_LAUNCH((colsum8_partial_kernel<float>), grid, dim3(256), 0, s, (const float*)in, ld, rows, cols, partial, stride_in), "col_sum");
@@ -773,6 +775,7 @@ extern "C" int mh_col_sum(const void* in, int64_t ld, int64_t rows, int cols, in
                     MH_LAUNCH((colsum_partial_kernel<float>), grid, dim3(256), 0, s, (const float*)in, ld, rows, cols, partial, stride_in), "col_sum");
   }
   MH_CHECK_LAUNCH();
+  mh_prof_note("P=%d acc=%d", n_partial, accumulate != 0);
   MH_LAUNCH(colsum_final_kernel, dim3((cols + 63) / 64, batch), dim3(1024), 0, s, partial, n_partial, cols, out, accumulate);
   MH_CHECK_LAUNCH();
   return MH_OK;
@@ -858,20 +861,23 @@ int mh_ln_bwd_rows(const void* x, const void* dy, const float* gamma, void* dx, 
   DropArgs da;
   int rcd = mh_drop_args(drop, &da);
   if (rcd) return rcd;
+  // (the launch note goes directly in front of each launch: an argument check that returns must not leave one behind for the next record)
+#define MH_LN_NOTE() mh_prof_note("rows=%lld H=%d panel=%d always=%d drop=%d", (long long)rows, H, m_panel != 0, always != 0, da.thr != 0 || da.mask)
   if (da.thr != 0 || da.mask || (always && dx_dropped)) {
     MH_CHECK_ARG(dx_dropped, "layernorm_bwd_drop: dropout needs the second output");
-#define MH_LNBD(T, N) MH_LAUNCH((ln_bwd_kernel<T, N, true>), dim3(n_partial), dim3(256), 0, s, (const T*)x, (const T*)dy, gamma, (T*)dx, pg, pb, rows, H, eps, (T*)dx_dropped, da, ldm, m_panel)
+#define MH_LNBD(T, N) MH_LN_NOTE(); MH_LAUNCH((ln_bwd_kernel<T, N, true>), dim3(n_partial), dim3(256), 0, s, (const T*)x, (const T*)dy, gamma, (T*)dx, pg, pb, rows, H, eps, (T*)dx_dropped, da, ldm, m_panel)
     if (H <= 512) { MH_DTYPE_SWITCH(dtype, MH_LNBD(bf16, 1), MH_LNBD(float, 1), "layernorm_bwd_drop"); }
     else if (H <= 1024) { MH_DTYPE_SWITCH(dtype, MH_LNBD(bf16, 2), MH_LNBD(float, 2), "layernorm_bwd_drop"); }
     else { MH_DTYPE_SWITCH(dtype, MH_LNBD(bf16, 4), MH_LNBD(float, 4), "layernorm_bwd_drop"); }
 #undef MH_LNBD
   } else {
-#define MH_LNB(T, N) MH_LAUNCH((ln_bwd_kernel<T, N>), dim3(n_partial), dim3(256), 0, s, (const T*)x, (const T*)dy, gamma, (T*)dx, pg, pb, rows, H, eps)
+#define MH_LNB(T, N) MH_LN_NOTE(); MH_LAUNCH((ln_bwd_kernel<T, N>), dim3(n_partial), dim3(256), 0, s, (const T*)x, (const T*)dy, gamma, (T*)dx, pg, pb, rows, H, eps)
     if (H <= 512) { MH_DTYPE_SWITCH(dtype, MH_LNB(bf16, 1), MH_LNB(float, 1), "layernorm_bwd"); }
     else if (H <= 1024) { MH_DTYPE_SWITCH(dtype, MH_LNB(bf16, 2), MH_LNB(float, 2), "layernorm_bwd"); }
     else { MH_DTYPE_SWITCH(dtype, MH_LNB(bf16, 4), MH_LNB(float, 4), "layernorm_bwd"); }
 #undef MH_LNB
   }
+#undef MH_LN_NOTE
   MH_CHECK_LAUNCH();
   return MH_OK;
 }
@@ -880,14 +886,17 @@ int mh_ln_bwd_fold(const float* partial, int n_partial, int H, float* dgamma, fl
   hipStream_t s = (hipStream_t)stream;
   const float* pg = partial;
   const float* pb = partial + (int64_t)n_partial * H;
-  // (a colsum_final block folds 64 columns: 4 partial-lanes x 64)
+  // (a colsum_final block folds 64 columns: 16 partial-lanes x 64)
   if (dbeta == dgamma + H) {   // the two gradients side by side (as the partials are): one launch folds both
+    mh_prof_note("P=%d acc=%d", n_partial, accumulate != 0);
     MH_LAUNCH(colsum_final_kernel, dim3((H + 63) / 64, 2), dim3(1024), 0, s, pg, n_partial, H, dgamma, accumulate);
     MH_CHECK_LAUNCH();
     return MH_OK;
   }
+  mh_prof_note("P=%d acc=%d", n_partial, accumulate != 0);
   MH_LAUNCH(colsum_final_kernel, dim3((H + 63) / 64, 1), dim3(1024), 0, s, pg, n_partial, H, dgamma, accumulate);
   MH_CHECK_LAUNCH();
+  mh_prof_note("P=%d acc=%d", n_partial, accumulate != 0);
   MH_LAUNCH(colsum_final_kernel, dim3((H + 63) / 64, 1), dim3(1024), 0, s, pb, n_partial, H, dbeta, accumulate);
   MH_CHECK_LAUNCH();
   return MH_OK;
@@ -935,6 +944,8 @@ extern "C" int mh_cross_entropy_bwd(const float* logits, int64_t ld, const int32
 
 extern "C" int mh_sqdiff_mean(const float* a, const float* b, float scale_a, float* out, int B, int64_t per_batch, mh_stream_t stream) {
   MH_CHECK_ARG(a && out && B > 0 && per_batch > 0, "sqdiff_mean: bad arguments");
+  // (every batch's rows start per_batch floats apart: with per_batch % 4 == 0 their alignment is the base pointers')
+  mh_prof_note("vec=%d", per_batch % 4 == 0 && (reinterpret_cast<uintptr_t>(a) & 15) == 0 && (!b || (reinterpret_cast<uintptr_t>(b) & 15) == 0));
   MH_LAUNCH(sqdiff_mean_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, a, b, scale_a, out, per_batch);
   MH_CHECK_LAUNCH();
   return MH_OK;
@@ -966,6 +977,7 @@ extern "C" int mh_scatter_add_rows(const float* src, const int32_t* ids, float* 
   const int nchunks = n >= 32 * 256 ? 32 : (int)((n + 255) / 256);
   const int64_t chunk = ((n + nchunks - 1) / nchunks + 63) / 64 * 64;
   hipStream_t s = (hipStream_t)stream;
+  mh_prof_note("chunks=%d E=%d", nchunks, E);
   MH_LAUNCH(scatter_rows_partial_kernel, dim3((V + SCATTER_RV - 1) / SCATTER_RV, nchunks), dim3(256), 4 * SCATTER_RV * 256 * sizeof(float), s, src, ids,
             (float*)workspace, n, E, V, chunk);
   MH_CHECK_LAUNCH();
