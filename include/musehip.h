@@ -717,6 +717,29 @@ int mh_denoiser_get_defer_ln(void);
  * lm_head row): out[n][v] = -sqrt(clamp((w_sqnorm[v] + x_sqnorm[n]) - 2 dots[n][v], 0, inf)); dots = x W^T from mh_gemm_bias_act (fp32). */
 int mh_distance_scores(const float* dots, int64_t ld, const float* w_sqnorm, const float* x_sqnorm, float* out, int64_t ldo, int64_t n, int V,
                        mh_stream_t stream);
+/* Token cross-entropy over those scores WITHOUT the [n, V] score tensor (_token_discrete_loss, models/diffusion.py:556-575, for a
+ * logits_mode 2 model; csrc/distance_logits.hip).  s[r][v] is mh_distance_scores' expression, recomputed from dots [n][ld] (fp32, ld >= V;
+ * columns V .. ld - 1 are padding and never enter a maximum or a sum), w_sqnorm [V] and x_sqnorm [n] (mh_row_sqnorm).
+ * fwd: lse[r] = log sum_v exp(s[r][v]) (maximum-shifted), nll[r] = lse[r] - s[r][ids[r]].  ids [n] int32 on the device; an id outside [0, V)
+ *   is MH_ERR_INVALID: the entry point copies the ids to the host and waits for `stream` to look at them (inside a stream capture it
+ *   cannot: there the kernel reads nothing for such an id and its nll is NaN).
+ * bwd: grad [n] = the gradient of nll; lse as fwd wrote it.  With p = exp(s - lse), dl = grad (p - [v == id]) and G = dl / (2 s):
+ *   d_dots [n][ld] = -2 G (padding columns written as 0), d_xn [n] = sum_v G (fixed order: reproducible).  The gradient of w_sqnorm is
+ *   -1/2 mh_col_sum(d_dots).  Where the clamp is active (d2 <= 0, s == 0) G is 0 - NOT the reference autograd's inf / NaN at d2 == 0:
+ *   a position that sits exactly on an embedding row must not poison a training step. */
+int mh_distance_ce_fwd(const float* dots, int64_t ld, const float* w_sqnorm, const float* x_sqnorm, const int32_t* ids, float* nll, float* lse,
+                       int64_t n, int V, mh_stream_t stream);
+int mh_distance_ce_bwd(const float* dots, int64_t ld, const float* w_sqnorm, const float* x_sqnorm, const int32_t* ids, const float* lse,
+                       const float* grad, float* d_dots, float* d_xn, int64_t n, int V, mh_stream_t stream);
+/* backward of mh_row_sqnorm: out[r][0 .. cols) = 2 (c_scale c[r]) x[r][0 .. cols); x [rows][ldx], out [rows][ldo], c [rows] the gradient
+ * of the squared norms (c_scale: 1, or -1/2 when c is mh_col_sum(d_dots) above - a power of two, so the product is exact) */
+int mh_sqnorm_bwd(const float* x, int64_t ldx, const float* c, float c_scale, float* out, int64_t ldo, int64_t rows, int cols,
+                  mh_stream_t stream);
+/* idx[n] = argmax_v of mh_distance_scores' expression with |x_n|^2 accumulated in the kernel, first index on ties (argmax_tokens of a
+ * logits_mode 2 model: run/sample.py:219-220 on models/network.py:94-104).  table [V, E], table_sqnorm [V] from mh_row_sqnorm; the
+ * kernel of mh_round_to_embedding / mh_logits_argmax with the square root applied before the comparison. */
+int mh_distance_argmax(const float* x, const float* table, const float* table_sqnorm, int32_t* idx, int64_t n_tokens, int E, int V,
+                       mh_stream_t stream);
 
 /* ---------------------------------------------------------------- training step on K32 panels (round 6)
  * The encoder layers of training_losses (models/diffusion.py:594-699 through models/network.py:151 -> HF BertLayer forward, and its

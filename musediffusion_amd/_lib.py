@@ -195,6 +195,10 @@ SIGNATURES = {
     "mh_gemm_dw_splits": (INT, [I64, INT, INT]),
     "mh_weight_prep": (INT, [VP, INT, INT, VP]),
     "mh_distance_scores": (INT, [VP, I64, VP, VP, VP, I64, I64, INT, VP]),
+    "mh_distance_ce_fwd": (INT, [VP, I64, VP, VP, VP, VP, VP, I64, INT, VP]),
+    "mh_distance_ce_bwd": (INT, [VP, I64, VP, VP, VP, VP, VP, VP, VP, I64, INT, VP]),
+    "mh_sqnorm_bwd": (INT, [VP, I64, VP, F32, VP, I64, I64, INT, VP]),
+    "mh_distance_argmax": (INT, [VP, VP, VP, VP, I64, INT, INT, VP]),
     "mh_gemm_desc_launch": (INT, [C.POINTER(GemmDesc), VP]),
     "mh_gemm_dw_bias_ex": (INT, [VP, I64, VP, I64, INT, VP, INT, I64, INT, INT, INT, VP]),
     "mh_layernorm_bwd_ex": (INT, [VP, VP, VP, VP, VP, I64, INT, INT, VP, VP, INT, VP, VP, INT, I64, INT, F32, INT, VP]),

@@ -4,7 +4,8 @@
 // the fp32 MFMA on gfx950) with fmaf chains, the reference's expression order for the distance
 // (emb_norm + arr_norm) - 2.0 * dot, clamp at 0, and first-index tie-breaking like torch.max /
 // torch.argmax.  One workgroup = 64 tokens x the whole vocabulary, vocabulary and embedding dim walked
-// in 64 x 64 LDS tiles; the [N, V] score matrix never exists in memory.
+// in 64 x 64 LDS tiles; the [N, V] score matrix never exists in memory.  Mode 2 is the argmax of get_logits with logits_mode 2
+// (models/network.py:94-104): the same distance under the square root of distance_scores_kernel (elementwise.hip).
 #include "common.h"
 
 #pragma clang fp contract(off)
@@ -13,7 +14,7 @@ namespace {
 
 constexpr int TLD = 68;  // padded LDS row (floats): rows tx+16b / 4ty+a read as float4 are conflict-free
 
-template <int MODE>  // 0: rounding (argmin distance)   1: logits (argmax x.W + b)
+template <int MODE>  // 0: rounding (argmin distance)   1: logits (argmax x.W + b)   2: distance logits (argmax -sqrt(distance), logits_mode 2)
 __global__ __launch_bounds__(256) void vocab_argmax_kernel(const float* __restrict__ x, const float* __restrict__ table,
                                                            const float* __restrict__ aux, int32_t* __restrict__ idx_out,
                                                            int64_t n_tokens, int E, int V) {
@@ -47,7 +48,7 @@ __global__ __launch_bounds__(256) void vocab_argmax_kernel(const float* __restri
         Ws[r * TLD + c] = in ? table[(int64_t)vr * E + e0 + c] : 0.f;
       }
       __syncthreads();
-      if (MODE == 0 && v0 == 0) {
+      if (MODE != 1 && v0 == 0) {
         // |x_n|^2, accumulated once (first vocabulary tile): lanes split the chunk, xor-reduce over tx
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
@@ -89,6 +90,11 @@ __global__ __launch_bounds__(256) void vocab_argmax_kernel(const float* __restri
             float dist = (av + xn[a]) - 2.0f * dot[a][b];
             dist = fmaxf(dist, 0.0f);
             score = -dist;
+          } else if (MODE == 2) {
+            // get_logits with logits_mode 2 (distance_scores_kernel's expression): the square root can merge two distances that
+            // mode 0 tells apart, and the first index must then win as it does in argmax(get_logits(x))
+            const float dist = (av + xn[a]) - 2.0f * dot[a][b];
+            score = -sqrtf(fmaxf(dist, 0.0f));
           } else {
             score = dot[a][b] + av;
           }
@@ -130,6 +136,16 @@ extern "C" int mh_logits_argmax(const float* x, const float* table, const float*
   MH_CHECK_ARG(n_tokens > 0 && E > 0 && V > 0, "logits_argmax: bad shape");
   MH_LAUNCH((vocab_argmax_kernel<1>), dim3((unsigned)((n_tokens + 63) / 64)), dim3(256), 0,
                      (hipStream_t)stream, x, table, bias, idx, n_tokens, E, V);
+  MH_CHECK_LAUNCH();
+  return MH_OK;
+}
+
+extern "C" int mh_distance_argmax(const float* x, const float* table, const float* table_sqnorm, int32_t* idx, int64_t n_tokens, int E, int V,
+                                  mh_stream_t stream) {
+  MH_CHECK_ARG(x && table && table_sqnorm && idx, "distance_argmax: null pointer");
+  MH_CHECK_ARG(n_tokens > 0 && E > 0 && V > 0, "distance_argmax: bad shape");
+  MH_LAUNCH((vocab_argmax_kernel<2>), dim3((unsigned)((n_tokens + 63) / 64)), dim3(256), 0,
+                     (hipStream_t)stream, x, table, table_sqnorm, idx, n_tokens, E, V);
   MH_CHECK_LAUNCH();
   return MH_OK;
 }

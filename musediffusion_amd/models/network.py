@@ -234,9 +234,18 @@ class TransformerNetModel(nn.Module):
         return out.view(*hidden_repr.shape[:-1], V)
 
     def argmax_tokens(self, hidden_repr):
-        """argmax(get_logits(x), -1) without materialising the logits (run/sample.py:219-220)."""
+        """argmax(get_logits(x), -1) without materialising the logits (run/sample.py:219-220), in the model's logits_mode."""
+        if self.logits_mode not in (1, 2):
+            raise NotImplementedError
         w, b = self.lm_head.weight.detach(), self.lm_head.bias.detach()
-        idx = ops.logits_argmax(hidden_repr.to(torch.float32), w, b)
+        if self.logits_mode == 2:
+            # |W_v|^2: the cache that follows the engine (refreshed with it when any parameter's version changes) while lm_head is tied
+            # to the embedding; after overload_embedding (utils/initialization.py:61-63) lm_head has rows of its own
+            tied = w.data_ptr() == self.word_embedding.weight.data_ptr()
+            wn = self.embedding_norms() if tied else ops.row_sqnorm(w)
+            idx = ops.distance_argmax(hidden_repr.to(torch.float32), w, wn)
+        else:
+            idx = ops.logits_argmax(hidden_repr.to(torch.float32), w, b)
         return idx.view(hidden_repr.shape[:-1]).long()
 
     @staticmethod

@@ -195,6 +195,44 @@ def logits_argmax(x, table, bias):
     return idx
 
 
+def distance_argmax(x, table, table_sqnorm):
+    """argmax_v -sqrt(clamp(|W_v|^2 + |x_n|^2 - 2 W_v.x_n, 0)), first index on ties (logits_mode 2), int32."""
+    x, table, table_sqnorm = _c(x, torch.float32), _c(table, torch.float32), _c(table_sqnorm, torch.float32)
+    V, E = table.shape
+    n = x.numel() // E
+    idx = torch.empty(n, device=x.device, dtype=torch.int32)
+    check(lib().mh_distance_argmax(ptr(x), ptr(table), ptr(table_sqnorm), ptr(idx), n, E, V, current_stream()), "mh_distance_argmax")
+    return idx
+
+
+def distance_ce_fwd(dots, w_sqnorm, x_sqnorm, ids32, V):
+    """dots [n, ld] fp32 -> (nll [n], lse [n]) of the logits_mode 2 scores against ids32 [n] int32."""
+    n, ld = dots.shape
+    nll = torch.empty(n, device=dots.device, dtype=torch.float32)
+    lse = torch.empty_like(nll)
+    check(lib().mh_distance_ce_fwd(ptr(dots), ld, ptr(w_sqnorm), ptr(x_sqnorm), ptr(ids32), ptr(nll), ptr(lse), n, V, current_stream()),
+          "mh_distance_ce_fwd")
+    return nll, lse
+
+
+def distance_ce_bwd(dots, w_sqnorm, x_sqnorm, ids32, lse, grad, V):
+    """-> (d_dots [n, ld] with zero padding columns, d_xn [n])."""
+    n, ld = dots.shape
+    d_dots = torch.empty_like(dots)
+    d_xn = torch.empty(n, device=dots.device, dtype=torch.float32)
+    check(lib().mh_distance_ce_bwd(ptr(dots), ld, ptr(w_sqnorm), ptr(x_sqnorm), ptr(ids32), ptr(lse), ptr(grad), ptr(d_dots), ptr(d_xn), n, V,
+                                   current_stream()), "mh_distance_ce_bwd")
+    return d_dots, d_xn
+
+
+def sqnorm_bwd(x, c, c_scale=1.0):
+    """2 (c_scale c[r]) x[r][:]: the gradient of the rows of x given the gradient c of their squared norms."""
+    rows, cols = x.shape
+    out = torch.empty_like(x)
+    check(lib().mh_sqnorm_bwd(ptr(x), cols, ptr(c), float(c_scale), ptr(out), cols, rows, cols, current_stream()), "mh_sqnorm_bwd")
+    return out
+
+
 def _mask_args(mask, x):
     """mask -> (int32 tensor, per_elem flag).  Accepts [B,L] (per token) or x-shaped (per element)."""
     if mask is None:

@@ -709,6 +709,35 @@ class _TokenCE(Function):
         return dl, None, None
 
 
+class _DistanceCE(Function):
+    """Per-token cross-entropy of the logits_mode 2 scores (network.py:94-104) against ids [N], from the fp32 product dots = x W^T
+    [N, pad64(V)] of a _Linear node without bias, x [N, Kp] fp32 and W [V, E]; the [N, V] scores are never stored (csrc/distance_logits.hip).
+    The gradient reaches x and W twice: through dots (returned to the _Linear node) and through the squared norms, 2 d_xn x and 2 d_wn W.
+    Where the clamp is active the gradient is 0, not the reference's inf / NaN."""
+
+    @staticmethod
+    def forward(ctx, dots, x, W, ids, V):
+        ids32 = ids.reshape(-1).to(torch.int32).contiguous()
+        Wd = W.detach()
+        wn, xn = ops.row_sqnorm(Wd), ops.row_sqnorm(x)
+        nll, lse = ops.distance_ce_fwd(dots, wn, xn, ids32, V)
+        ctx.save_for_backward(dots, x, Wd, ids32, lse, wn, xn)
+        ctx.V = V
+        return nll
+
+    @staticmethod
+    def backward(ctx, g):
+        dots, x, Wd, ids32, lse, wn, xn = ctx.saved_tensors
+        V = ctx.V
+        d_dots, d_xn = ops.distance_ce_bwd(dots, wn, xn, ids32, lse, g.contiguous(), V)
+        dx = ops.sqnorm_bwd(x, d_xn) if ctx.needs_input_grad[1] else None
+        dW = None
+        if ctx.needs_input_grad[2]:
+            colsum = _col_sum(d_dots, dots.shape[0], V, MH_F32)                                     # = -2 d_wn
+            dW = ops.sqnorm_bwd(Wd, colsum, -0.5)
+        return d_dots, dx, dW, None, None
+
+
 # ---------------------------------------------------------------------------------------------- composites
 class _StackRows(Function):
     """The [3H, K] weight of the fused query | key | value projection as a TAPE node: with _WeightPrep's packed working copy its values
@@ -1106,12 +1135,19 @@ def denoiser_forward_with_grad(model, x, timesteps):
 
 def _token_nll(net, x, ids, mask=None):
     """_token_discrete_loss (diffusion.py:556-575): CE of get_logits(x) against ids, averaged over positions
-    (mask-weighted when a mask is given).  The logits GEMM runs in fp32 on the exact-fp32 MFMA."""
+    (mask-weighted when a mask is given).  The logits GEMM runs in fp32 on the exact-fp32 MFMA.  logits_mode 2 (network.py:94-104): the
+    same GEMM without the bias, then the distance scores' CE (lm_head.bias takes no part and gets no gradient, as in the reference)."""
+    if net.logits_mode not in (1, 2):
+        raise NotImplementedError
     B, L, E = x.shape
     V = net.lm_head.weight.shape[0]
     xin = _Cast.apply(x.reshape(B * L, E).float(), MH_F32, True)
-    logits = _Linear.apply(xin, net.lm_head.weight, net.lm_head.bias, None, None, MH_F32)         # [N, pad64(V)] fp32
-    nll = _TokenCE.apply(logits, ids, V).view(B, L)
+    if net.logits_mode == 2:
+        dots = _Linear.apply(xin, net.lm_head.weight, None, None, None, MH_F32)                   # [N, pad64(V)] fp32
+        nll = _DistanceCE.apply(dots, xin, net.lm_head.weight, ids, V).view(B, L)
+    else:
+        logits = _Linear.apply(xin, net.lm_head.weight, net.lm_head.bias, None, None, MH_F32)     # [N, pad64(V)] fp32
+        nll = _TokenCE.apply(logits, ids, V).view(B, L)
     if mask is not None:
         m = mask.to(nll.device, torch.float32)
         return (nll * m).sum(dim=-1) / m.sum(dim=-1)
