@@ -553,6 +553,42 @@ int mh_msim_vectors(const int32_t* tokens, const int32_t* lens, float* out, int3
 int mh_controllability_counts(const int32_t* tokens, const int32_t* lens, const int32_t* metas, int meta_ld, int32_t* out, int B,
                               int L, mh_stream_t stream);
 
+/* ---- sampled tokens -> restored note sequences -> notes and chord markers (csrc/decode.hip): what the reference does per sequence on
+ * the host between the sampler's [B, L] token ids and the MIDI container (run/sample.py:222, SequenceToMidi.decode).  One block per
+ * row, rows of at most mh_batch_max_row() tokens, int32 throughout.  Any token value and any mask content are legal input: a row the
+ * reference could not decode gets a status, and nothing is read or written outside the buffers. */
+enum mh_decode_status {
+  MH_DECODE_OK = 0,
+  MH_DECODE_NO_EOS = 1,          /* remove_padding: SequenceToMidiError("NO EOS TOKEN") */
+  MH_DECODE_RESTORE_FAILED = 2,  /* restore_chord: more than one Bar too many, "RESTORE_CHORD FROM META FAILED" */
+  MH_DECODE_ONCE_FAILED = 3,     /* validate_once: "VALIDATION OF SEQUENCE FAILED" */
+  MH_DECODE_STRICT_FAILED = 4,   /* validate_rigidly: "STRICT VALIDATION OF SEQUENCE FAILED" */
+  MH_DECODE_REF_INDEXERROR = 5,  /* the reference raises IndexError (no SequenceToMidiError: it ends the reference's run): restore_chord
+                                    indexing a Bar that is not there, or validate_rigidly reading past a truncated last note */
+  MH_DECODE_BAD_META = 6,        /* bpm / key / time-signature token outside 561..600 / 602..625 / 627..630 (the reference: KeyError from
+                                    its tables; a bpm token out of range it accepts, but 560 is tempo 0, which no MIDI file can hold, and the encoder
+                                    never writes it), or - ours - sum(mask) outside [0, L] */
+  MH_DECODE_OVERFLOW = 7         /* ours, not the reference's: the restored row is longer than ld_out (or, with a len_meta of 0, than
+                                    mh_batch_max_row()), or the row holds more notes / chords than max_notes / max_chords */
+};
+/* utils/decode_util.py:192-199 split_meta_midi = :73-84 remove_padding + :85-142 restore_chord, per row of tokens / input_mask [B, L]:
+ * len_meta = L - sum(mask), meta = seq[:len_meta - 1], notes = seq[len_meta:] cut after the first EOS, then the chord tokens of
+ * meta[11:] are spliced back into the notes (three entry branches by the number of Bars against the number of 432s, then one step per
+ * chord pair), quirks kept.  restored [B, ld_out]: the sequence, zero after restored_len[b] (0 unless status[b] is OK);
+ * meta [B, 11]: meta[:11], zero where the meta is shorter; status [B]: OK, NO_EOS, RESTORE_FAILED, REF_INDEXERROR, BAD_META, OVERFLOW. */
+int mh_restore_chord(const int32_t* tokens, const int32_t* input_mask, int32_t* restored, int32_t* restored_len, int32_t* meta,
+                     int32_t* status, int B, int L, int ld_out, mh_stream_t stream);
+/* utils/decode_util.py:145-156 validate_once (over the whole restored row), then commu/preprocessor/encoder/encoder.py:71-97 decode and
+ * encoder_utils.py:370-497 word_to_event / write_midi up to the container: rows whose status[b] is OK on entry are validated and decoded,
+ * the others pass through.  restored [B, ld] / restored_len / meta: mh_restore_chord's outputs.  strict != 0 adds validate_rigidly, read
+ * from `validate` = mh_validate_tokens(restored, restored_len) [B, 3] (may be NULL when strict == 0).
+ * notes [B, max_notes, 4] = (start tick, end tick, pitch, velocity) and chords [B, max_chords, 2] = (tick, chord token 195..303), in
+ * token order, 480 ticks per beat; entries past the counts are not written.  counts [B, 3] = (notes, chords, out-of-vocabulary tokens:
+ * 0 or >= 560), zero for rows that are not decoded.  status [B] in / out: + ONCE_FAILED, STRICT_FAILED, REF_INDEXERROR, BAD_META, OVERFLOW. */
+int mh_decode_events(const int32_t* restored, const int32_t* restored_len, const int32_t* meta, const int32_t* validate, int strict,
+                     int32_t* notes, int32_t* chords, int32_t* counts, int32_t* status, int B, int ld, int max_notes, int max_chords,
+                     mh_stream_t stream);
+
 /* ---------------------------------------------------------------- train-mode dropout
  * Reference: nn.Dropout(dropout) after the embedding LayerNorm (MuseDiffusion/models/network.py:76, :149) and the HF BertEncoder's
  * hidden dropout (after the attention-output and FFN-output dense layers, before residual + LayerNorm) and attention-probability

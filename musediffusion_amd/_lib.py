@@ -185,6 +185,8 @@ SIGNATURES = {
     "mh_controllability_counts": (INT, [VP, VP, VP, INT, VP, INT, INT, VP]),
     "mh_msim_vectors": (INT, [VP, VP, VP, VP, INT, INT, F32, VP]),
     "mh_validate_tokens": (INT, [VP, VP, VP, INT, INT, VP]),
+    "mh_restore_chord": (INT, [VP, VP, VP, VP, VP, VP, INT, INT, INT, VP]),
+    "mh_decode_events": (INT, [VP, VP, VP, VP, INT, VP, VP, VP, VP, INT, INT, INT, INT, VP]),
     "mh_scale_rows": (INT, [VP, VP, VP, VP, INT, INT, I64, INT, VP]),
     "mh_adamw_ema_step": (INT, [VP, VP, INT, C.POINTER(OptHParams), VP]),
     "mh_grad_norm": (INT, [VP, VP, INT, VP, VP, VP]),

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the device batch producers / token validators at a BASELINE-sized batch
-(512 sequences, ~1000 tokens each), with the numpy oracle (= the reference's per-token Python loops restated) beside it."""
+(512 sequences, ~1000 tokens each), with the numpy oracle (= the reference's per-token Python loops restated) beside it; then
+the decode path (csrc/decode.hip) on 512 x 1024 generated rows beside its numpy restatement (profiles/decode_events.txt)."""
 import os
 import sys
 import time
@@ -62,3 +63,45 @@ for name, fn, nbytes, cpu in cases:
         dt = (time.perf_counter() - t0) / 64 * len(rows)
         line += "   | numpy/python oracle, 1 core: %8.1f ms per batch (%.0fx)" % (dt * 1e3, dt * 1e6 / us)
     print(line, flush=True)
+
+# ---- decode: sampled token rows -> restored note sequences -> notes / chord markers (csrc/decode.hip), 512 x 1024 from the tests' row
+# generator (rows that decode and rows of every failure kind), event-timed per kernel, beside the numpy restatement of the same path
+# (tests/decode_ref.py = the reference's per-sequence host loop restated) on one core.  A single box's numbers; nothing gates on them.
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+import decode_ref as dr  # noqa: E402
+from musediffusion_amd._lib import current_stream, lib  # noqa: E402
+
+tok_np, mask_np, kinds = dr.make_batch(0, 1024, [dr.BATCH_KINDS[i % len(dr.BATCH_KINDS)] for i in range(512)])
+tok, msk = torch.from_numpy(tok_np).cuda(), torch.from_numpy(mask_np).cuda()
+B, L, LD, MAXN, MAXC = 512, 1024, 2048, 513, 1025
+restored, rlen, meta = torch.empty(B, LD, dtype=torch.int32, device="cuda"), torch.empty(B, dtype=torch.int32, device="cuda"), torch.empty(B, 11, dtype=torch.int32, device="cuda")
+st0, st = torch.empty(B, dtype=torch.int32, device="cuda"), torch.empty(B, dtype=torch.int32, device="cuda")
+notes_d, chords_d = torch.zeros(B, MAXN, 4, dtype=torch.int32, device="cuda"), torch.zeros(B, MAXC, 2, dtype=torch.int32, device="cuda")
+counts = torch.empty(B, 3, dtype=torch.int32, device="cuda")
+
+
+def restore():
+    lib().mh_restore_chord(tok.data_ptr(), msk.data_ptr(), restored.data_ptr(), rlen.data_ptr(), meta.data_ptr(), st0.data_ptr(), B, L, LD, current_stream())
+
+
+def events():
+    st.copy_(st0)                                        # the status is in / out: start every repetition from restore_chord's
+    lib().mh_decode_events(restored.data_ptr(), rlen.data_ptr(), meta.data_ptr(), None, 0, notes_d.data_ptr(), chords_d.data_ptr(),
+                           counts.data_ptr(), st.data_ptr(), B, LD, MAXN, MAXC, current_stream())
+
+
+us_restore = timeit(restore)
+us_copy = timeit(lambda: st.copy_(st0))
+us_events = timeit(events) - us_copy
+us_all = timeit(lambda: mdec.decode_tokens(tok, msk))
+t0 = time.perf_counter()
+ref_rows = dr.decode_rows(tok_np[:64], mask_np[:64], LD, MAXN, MAXC)
+host_ms = (time.perf_counter() - t0) / 64 * B * 1e3
+torch.cuda.synchronize()
+assert [int(s) for s in st[:64].cpu()] == [r["status"] for r in ref_rows]
+n_ok = int((st == 0).sum())
+print("decode: %d rows x %d tokens (%d decode, %d notes, %d chord markers)" % (B, L, n_ok, int(counts[:, 0].sum()), int(counts[:, 1].sum())))
+print("%-18s %8.1f us" % ("mh_restore_chord", us_restore))
+print("%-18s %8.1f us" % ("mh_decode_events", us_events))
+print("%-18s %8.1f us  (allocation, zero fill and both kernels)   | numpy/python restatement, 1 core: %8.1f ms per batch (%.0fx the two kernels)"
+      % ("decode_tokens", us_all, host_ms, host_ms * 1e3 / (us_restore + us_events)), flush=True)
