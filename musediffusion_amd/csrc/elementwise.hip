@@ -231,6 +231,11 @@ inline bool step_epilogue_vec_ok(const float* model_out, const float* x_t, const
   return E % 4 == 0 && per_batch % E == 0 && (int64_t)B * per_batch / 4 < (1ll << 32) && al(model_out) && al(x_t) && al(noise) && al(table) &&
          al(x_start) && al(out) && al(pred) && al(mean);
 }
+// launch note of an update kernel: the classes of its runtime arguments that select a path the kernel text does not show
+// (x0 source, mask form, per-batch coefficients, noise source, whether the slot fold runs)
+inline void step_epilogue_note(const char* x0, const int32_t* mask, int mask_per_elem, int coef_per_batch, const char* noise, int fold) {
+  mh_prof_note("x0=%s mask=%s cpb=%d noise=%s fold=%d", x0, !mask ? "none" : (mask_per_elem ? "elem" : "row"), coef_per_batch != 0, noise, fold);
+}
 }  // namespace
 
 __global__ __launch_bounds__(256) void trunc_normal_kernel(float* __restrict__ out, int64_t n, int64_t first, float bound, uint32_t seed_lo,
@@ -401,6 +406,7 @@ extern "C" int mh_p_sample_epilogue(const float* model_out, const float* x_t, co
   MH_CHECK_ARG(!round_idx || table, "p_sample_epilogue: round_idx needs the embedding table");
   MH_CHECK_ARG(!mask || x_start, "p_sample_epilogue: mask needs x_start");
   MH_CHECK_ARG(B > 0 && per_batch > 0 && E > 0 && per_batch % E == 0, "p_sample_epilogue: bad shape");
+  step_epilogue_note(round_idx ? "idx" : "model", mask, mask_per_elem, coef_per_batch, noise ? "given" : "none", 0);
   if (step_epilogue_vec_ok(model_out, x_t, noise, table, x_start, out, pred_xstart, mean_out, B, per_batch, E)) {
     const int64_t ng = (int64_t)B * per_batch / 4;
     MH_LAUNCH((step_epilogue4_kernel<false>), dim3(ew_grid(ng)), dim3(EW_BLOCK), 0, (hipStream_t)stream, model_out, x_t, noise, round_idx, table, coef,
@@ -422,6 +428,7 @@ extern "C" int mh_ddim_epilogue(const float* model_out, const float* x_t, const 
   MH_CHECK_ARG(!round_idx || table, "ddim_epilogue: round_idx needs the embedding table");
   MH_CHECK_ARG(!mask || x_start, "ddim_epilogue: mask needs x_start");
   MH_CHECK_ARG(B > 0 && per_batch > 0 && E > 0 && per_batch % E == 0, "ddim_epilogue: bad shape");
+  step_epilogue_note(round_idx ? "idx" : "model", mask, mask_per_elem, coef_per_batch, noise ? "given" : "none", 0);
   if (step_epilogue_vec_ok(model_out, x_t, noise, table, x_start, out, pred_xstart, nullptr, B, per_batch, E)) {
     const int64_t ng = (int64_t)B * per_batch / 4;
     MH_LAUNCH((step_epilogue4_kernel<true>), dim3(ew_grid(ng)), dim3(EW_BLOCK), 0, (hipStream_t)stream, model_out, x_t, noise, round_idx, table, coef,
@@ -447,6 +454,7 @@ extern "C" int mh_step_epilogue_slots(int ddim, const float* x_t, const float* n
   const int64_t ng = (int64_t)B * per_batch / 4;
   const float* none = nullptr;
   const int32_t* nidx = nullptr;
+  step_epilogue_note("slots", mask, mask_per_elem, coef_per_batch, rng ? "rng" : (noise ? "given" : "none"), nslots != 0);
   if (rng) {
     const StepRng r{(uint32_t)rng->seed, (uint32_t)(rng->seed >> 32), rng->stream_id, rng->bound, rng->step_counter, (uint64_t)(rng->first_elem >> 2)};
     if (ddim)

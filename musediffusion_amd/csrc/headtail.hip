@@ -686,7 +686,11 @@ extern "C" int mh_down_proj_round_fused(const void* X, int64_t ldx, const void* 
   }
   const int rpb = H == 768 ? 32 : 64;
   const dim3 grid((unsigned)((rows + rpb - 1) / rpb));
-  mh_prof_note("tail+round%s rows=%lld E=%d H=%d V=%d", upd ? "+update" : "", (long long)rows, E, H, V);
+  if (upd)
+    mh_prof_note("tail+round+update rows=%lld E=%d H=%d V=%d upd=1 ddim=%d noise=%s mask=%s", (long long)rows, E, H, V, upd->ddim != 0,
+                 upd->rng ? "rng" : (upd->noise ? "given" : "none"), !upd->mask ? "none" : (upd->mask_per_elem ? "elem" : "row"));
+  else
+    mh_prof_note("tail+round rows=%lld E=%d H=%d V=%d upd=0", (long long)rows, E, H, V);
   if (H == 768) MH_LAUNCH((tail_fused_kernel<768, 4, 32>), grid, dim3(768), 0, (hipStream_t)stream, g);   // 12 waves x 4 table tiles of 16 rows = 768
   else MH_LAUNCH((tail_fused_kernel<512, 6>), grid, dim3(512), 0, (hipStream_t)stream, g);
   MH_CHECK_LAUNCH();

@@ -81,6 +81,7 @@ int launch_ln(const void* x, int64_t ldx, const float* xf32, const float* pos, c
               const int32_t* emb_row, const float* gamma, const float* beta, void* out, int64_t rows, int L, int H,
               float eps, bool add, hipStream_t s) {
   dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+  mh_prof_note("x=%s out=%s add=%d rows=%lld H=%d", xf32 ? "f32" : (sizeof(T) == 2 ? "bf16" : "f32"), sizeof(T) == 2 ? "bf16" : "f32", (int)add, (long long)rows, H);
   if (add)
     MH_LAUNCH((ln_kernel<T, true>), grid, block, 0, s, (const T*)x, ldx, xf32, pos, emb_t, emb_row, gamma,
                        beta, (T*)out, rows, L, H, eps);
@@ -233,10 +234,13 @@ template <bool ADD>
 int launch_ln_panel(const void* x, int64_t ldx, const float* xf32, const float* pos, const float* emb_t,
                     const int32_t* emb_row, const float* gamma, const float* beta, void* out, int64_t ldo, int64_t rows,
                     int L, int H, float eps, hipStream_t s) {
+  // the launch note is set inside the cases: an unsupported width launches nothing and must leave no note behind for the next launch
+#define MH_LNP_NOTE() mh_prof_note("x=%s add=%d rows=%lld H=%d", xf32 ? "f32" : "bf16", (int)ADD, (long long)rows, H)
   if (g_ln_rows4 && (H / 32) % 4 == 0) {
     dim3 grid4((unsigned)((rows + 15) / 16)), block4(256);
 #define MH_LNP4(N)                                                                                                      \
   case N:                                                                                                              \
+    MH_LNP_NOTE();                                                                                                     \
     MH_LAUNCH((ln_panel4_kernel<N, ADD>), grid4, block4, 0, s, (const bf16*)x, ldx, xf32, pos, emb_t, emb_row, gamma, beta, \
               (bf16*)out, ldo, rows, L, eps);                                                                          \
     break;
@@ -253,6 +257,7 @@ int launch_ln_panel(const void* x, int64_t ldx, const float* xf32, const float* 
   dim3 grid((unsigned)((rows + 63) / 64)), block(256);
 #define MH_LNP(N)                                                                                                      \
   case N:                                                                                                              \
+    MH_LNP_NOTE();                                                                                                     \
     MH_LAUNCH((ln_panel_kernel<N, ADD>), grid, block, 0, s, (const bf16*)x, ldx, xf32, pos, emb_t, emb_row, gamma, beta, \
               (bf16*)out, ldo, rows, L, eps);                                                                          \
     break;
@@ -263,6 +268,7 @@ int launch_ln_panel(const void* x, int64_t ldx, const float* xf32, const float* 
       return MH_ERR_UNSUPPORTED;
   }
 #undef MH_LNP
+#undef MH_LNP_NOTE
   MH_CHECK_LAUNCH();
   return MH_OK;
 }

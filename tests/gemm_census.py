@@ -14,12 +14,13 @@ import numpy as np
 GEMM_FAMILY = ("gemm_kernel", "gemm_big_kernel", "gemm_strip_kernel", "gemm_tn_kernel", "split_gemm_kernel", "split_gemm_ln_kernel")
 
 
-def philox7(c, k0, k1):
-    """Philox4x32 with 7 rounds on uint64 arrays holding 32-bit words: counter words c[0..3], key (k0, k1) -> 4 output words"""
+def philox7(c, k0, k1, rounds=7):
+    """Philox4x32 with `rounds` rounds (7: the dropout sites; 10: the truncated normal, tests/step_ref.py) on uint64 arrays holding 32-bit
+    words: counter words c[0..3], key (k0, k1) -> 4 output words"""
     c = [np.asarray(x).astype(np.uint64) for x in c]
     k0, k1 = np.uint64(k0), np.uint64(k1)
     M0, M1, W0, W1, MASK = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57), np.uint64(0x9E3779B9), np.uint64(0xBB67AE85), np.uint64(0xFFFFFFFF)
-    for _ in range(7):
+    for _ in range(rounds):
         p0, p1 = M0 * c[0], M1 * c[2]
         n0 = (p1 >> np.uint64(32)) ^ c[1] ^ k0
         n2 = (p0 >> np.uint64(32)) ^ c[3] ^ k1
