@@ -589,6 +589,50 @@ int mh_decode_events(const int32_t* restored, const int32_t* restored_len, const
                      int32_t* notes, int32_t* chords, int32_t* counts, int32_t* status, int B, int ld, int max_notes, int max_chords,
                      mh_stream_t stream);
 
+/* ---- notes and a chord progression -> event words -> model rows (csrc/encode.hip): the way in, the inverse of the decode path above.
+ * What the reference does per MIDI file on the host: commu/preprocessor/encoder/encoder.py:21-69 EventSequenceEncoder.encode with
+ * encoder_utils.py:184-368 from the note list onward, then MuseDiffusion/data/preprocess.py:36-56 merge_and_mask.  One block per row,
+ * int32 throughout.  Any note values, counts and parameters are legal input: a row the reference could not encode gets a status, and
+ * nothing is read or written outside the buffers. */
+enum mh_encode_status {
+  MH_ENCODE_OK = 0,
+  MH_ENCODE_EMPTY = 1,         /* no notes (n_notes <= 0): the reference raises IndexError on note_items[-1] */
+  MH_ENCODE_NO_CHORDS = 2,     /* an empty progression (n_slots <= 0): extract_events returns None and encode fails on it */
+  MH_ENCODE_BAD_TIMEBASE = 3,  /* ticks_per_bar < 128, so int(ticks_per_bar / 128), np.arange's step, is 0: ZeroDivisionError.  Ours as well:
+                                  ticks_per_beat, numerator or denominator <= 0, ticks_per_bar > 2^24, fewer than one beat per bar */
+  MH_ENCODE_BAD_CHORDS = 4,    /* ours, not the reference's: n_slots is no multiple of the chords per bar (2 * int(ticks_per_bar /
+                                  ticks_per_beat)); np.array_split would split such a progression into uneven "bars" and go on */
+  MH_ENCODE_OVERFLOW = 5       /* ours: n_notes > max_notes or mh_encode_max_notes(), n_slots > max_slots or mh_encode_max_slots(), measures +
+                                  slots + notes > 4096, more words than ld; in mh_merge_and_mask: the rows do not fit cap */
+};
+int mh_encode_max_notes(void);
+int mh_encode_max_slots(void);
+/* notes [B, max_notes, 4] = (start tick, end tick, pitch, velocity), n_notes [B] of them per row - the layout mh_decode_events writes.
+ * params [B, 5] = (ticks_per_beat, numerator, denominator, ceil(num_measures), is_incomplete_measure as 0 / 1).
+ * chord_slots [B, max_slots, 2] = (name id, token) per slot of the progression, n_slots [B] of them: ids are equal where the lowercased
+ * full names are (detect_chord compares whole strings); token = event2word of the name cut at '/' and '(' after add_flat_chord2map and
+ * abstract_chord_types, or -1 where the reference prints "OOV".  The string work is the host's; all arithmetic is the kernel's.
+ * words [B, ld] (ld <= mh_batch_max_row()): the event words in the reference's order, ending in the EOS token 1, zero past length[b]
+ * (0 unless status[b] is OK); counts [B, 2] = (events before unknown ones are dropped, "OOV" lines the reference prints); status [B].
+ * Ours: is_incomplete_measure is read as a flag (any non-zero value is 1), where the reference computes with the raw value
+ * (tick_per_bar * is_incomplete_measure, i + 1 - is_incomplete_measure); for 0 / 1 / False / True, all it documents, the two agree.
+ * Quirks kept: order (start, pitch, input order); downbeats up to the end of the LAST sorted note, notes outside them lost; first
+ * argmin for position and duration; velocity below 2 -> Note Velocity_63 + an OOV line; pitch outside 0..127 -> no Note On word + an
+ * OOV line; a duration index above 127 -> Note Duration_127; float64 chord positions; chord events before note events at equal time. */
+int mh_encode_events(const int32_t* notes, const int32_t* n_notes, const int32_t* params, const int32_t* chord_slots,
+                     const int32_t* n_slots, int32_t* words, int32_t* length, int32_t* counts, int32_t* status, int B, int max_notes,
+                     int max_slots, int ld, mh_stream_t stream);
+/* data/preprocess.py:36-56 per row: input_ids = src + [trg[j - 1], trg[j] for every chord token 195 <= trg[j] <= 303] + [1] + trg
+ * without those; input_mask = 0 on src + pairs + [1], 1 on the rest.  j - 1 == -1 is the last element (numpy's negative index);
+ * adjacent chord tokens give overlapping pairs, gathered twice and removed once.  src [B, S] with src_len [B] tokens per row (NULL = S);
+ * words [B, ld] / lengths [B]: mh_encode_events' outputs (S, ld <= mh_batch_max_row()); status_in [B] (NULL = all OK): a row that is not
+ * OK gets length 0 and keeps its status.  Output as ragged values + offsets, what mh_ragged_to_padded and the corruptions take:
+ * ids / mask [cap], offsets [B + 1] int64 (three launches: lengths, their scan, the rows), length [B], status [B].  Rows that do not
+ * fit cap get length 0 and OVERFLOW; cap >= B * (S + 1 + 2 * ld) always fits. */
+int mh_merge_and_mask(const int32_t* src, const int32_t* src_len, const int32_t* words, const int32_t* lengths, const int32_t* status_in,
+                      int32_t* ids, int32_t* mask, int64_t* offsets, int32_t* length, int32_t* status, int B, int S, int ld, int64_t cap,
+                      mh_stream_t stream);
+
 /* ---------------------------------------------------------------- train-mode dropout
  * Reference: nn.Dropout(dropout) after the embedding LayerNorm (MuseDiffusion/models/network.py:76, :149) and the HF BertEncoder's
  * hidden dropout (after the attention-output and FFN-output dense layers, before residual + LayerNorm) and attention-probability

@@ -187,6 +187,10 @@ SIGNATURES = {
     "mh_validate_tokens": (INT, [VP, VP, VP, INT, INT, VP]),
     "mh_restore_chord": (INT, [VP, VP, VP, VP, VP, VP, INT, INT, INT, VP]),
     "mh_decode_events": (INT, [VP, VP, VP, VP, INT, VP, VP, VP, VP, INT, INT, INT, INT, VP]),
+    "mh_encode_max_notes": (INT, []),
+    "mh_encode_max_slots": (INT, []),
+    "mh_encode_events": (INT, [VP, VP, VP, VP, VP, VP, VP, VP, VP, INT, INT, INT, INT, VP]),
+    "mh_merge_and_mask": (INT, [VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, INT, INT, INT, I64, VP]),
     "mh_scale_rows": (INT, [VP, VP, VP, VP, INT, INT, I64, INT, VP]),
     "mh_adamw_ema_step": (INT, [VP, VP, INT, C.POINTER(OptHParams), VP]),
     "mh_grad_norm": (INT, [VP, VP, INT, VP, VP, VP]),

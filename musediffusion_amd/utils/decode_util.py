@@ -1,8 +1,8 @@
 """Device versions of MuseDiffusion/utils/decode_util.py: the batch layout and token checks and the
 decode path from sampled token rows to notes, chord markers and Standard MIDI Files (split_meta_midi / restore_chord /
 validation / commu's word_to_event + write_midi: csrc/decode.hip; the file itself is written by a small host writer here).
-The meta ENCODER (meta dict -> tokens, commu's MetaEncoder) stays out of scope: `meta_to_batch` takes the already encoded
-meta + chord tokens."""
+The way in - MetaToSequence, encode_notes, merge_and_mask, encode_batch (utils/encode_util.py, csrc/encode.hip) - is re-exported
+here, where the reference keeps MetaToSequence and meta_to_batch; `read_midi` is `write_midi`'s counterpart."""
 import os
 import struct
 
@@ -10,10 +10,16 @@ import numpy as np
 import torch
 
 from .._lib import check, current_stream, lib, ptr, require_device
+from .encode_util import (EncodedBatch, MetaToSequence, UnprocessableMidiError, chord_slots, encode_batch, encode_notes,  # noqa: F401
+                          merge_and_mask)
 
 
-def meta_to_batch(encoded_meta, batch_size, seq_len, device="cuda"):
-    """decode_util.py:221-230: input_ids[:, :len(meta)] = meta, input_mask = 1 except [:, :len(meta) + 1] = 0 (int32)"""
+def meta_to_batch(midi_meta_dict_or_tokens, batch_size, seq_len, device="cuda"):
+    """decode_util.py:221-230: input_ids[:, :len(meta)] = meta, input_mask = 1 except [:, :len(meta) + 1] = 0 (int32).  A dict is the
+    reference's argument and goes through MetaToSequence first; a sequence is the already encoded meta + chord tokens."""
+    encoded_meta = midi_meta_dict_or_tokens
+    if isinstance(encoded_meta, dict):
+        encoded_meta = MetaToSequence().execute(encoded_meta)
     meta = torch.as_tensor(encoded_meta, dtype=torch.int32).to(device).contiguous()
     ids = torch.empty(batch_size, seq_len, device=device, dtype=torch.int32)
     mask = torch.empty_like(ids)
@@ -183,6 +189,86 @@ def write_midi(path, notes, chords, meta):
         t1.append((end, 1, bytes([0x80, pitch, 0])))                                 # at one tick, offs go before ons
     with open(path, "wb") as f:
         f.write(b"MThd" + struct.pack(">IHHH", 6, 1, 2, TICKS_PER_BEAT) + _track(t0) + _track(t1))
+
+
+def _read_vlq(data, i):
+    n = 0
+    while True:
+        b = data[i]
+        i += 1
+        n = (n << 7) | (b & 0x7F)
+        if not b & 0x80:
+            return n, i
+
+
+def read_midi(path):
+    """Standard MIDI File, format 0 or 1 -> (ticks_per_beat, notes int32 [k, 4] = (start tick, end tick, pitch, velocity)) of the first
+    track that holds a note, all channels together, in the order the notes START; no third-party package.  Running status is followed;
+    a note-on of velocity 0 is a note-off; a note-off closes the oldest open note of its pitch and channel; a note still open at the
+    end of its track is closed there.  A file that is cut short, or whose events run past their track chunk, raises ValueError.
+    This is NOT miditoolkit's instrument grouping (which splits a track by channel and program and names instruments[0] the first of
+    those): for the single-instrument files write_midi and ComMU produce the two agree."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if data[:4] != b"MThd" or len(data) < 14:
+        raise ValueError("read_midi: %s is no Standard MIDI File" % (path,))
+    hlen, fmt, ntrk, division = struct.unpack(">IHHH", data[4:14])
+    if fmt > 1 or division & 0x8000:
+        raise ValueError("read_midi: format %d / SMPTE time division are not supported" % fmt)
+    i = 8 + hlen
+    for _ in range(ntrk):
+        if data[i:i + 4] != b"MTrk":
+            raise ValueError("read_midi: track chunk expected at byte %d" % i)
+        if i + 8 > len(data):
+            raise ValueError("read_midi: %s is truncated in a track header" % (path,))
+        end = i + 8 + struct.unpack(">I", data[i + 4:i + 8])[0]
+        if end > len(data):
+            raise ValueError("read_midi: %s is truncated: the track at byte %d says it ends at byte %d of %d" % (path, i, end, len(data)))
+        try:
+            notes, now = _read_track(data[i + 8:end])
+        except IndexError:
+            raise ValueError("read_midi: %s: an event runs past the end of the track at byte %d" % (path, i)) from None
+        if notes:
+            return division, np.array([[s, now if e is None else e, p, v] for s, e, p, v in notes], np.int32)
+        i = end
+    return division, np.zeros((0, 4), np.int32)
+
+
+def _read_track(data):
+    """the body of one MTrk chunk -> ([start, end or None, pitch, velocity] per note in start order, the track's last tick).  Every
+    read is inside `data`: an event that runs past the chunk raises IndexError, which read_midi reports as its ValueError."""
+    i, end = 0, len(data)
+    now, status, running, open_notes, notes = 0, 0, 0, {}, []
+    while i < end:
+        delta, i = _read_vlq(data, i)
+        now += delta
+        if data[i] & 0x80:
+            status = data[i]
+            i += 1
+            running = status if status < 0xF0 else 0                             # only channel messages leave a running status
+        else:
+            status = running
+        if status == 0xFF:                                                      # meta event: type, length, data
+            n, i = _read_vlq(data, i + 1)
+            i += n
+        elif status in (0xF0, 0xF7):                                             # system exclusive
+            n, i = _read_vlq(data, i)
+            i += n
+        elif status >> 4 in (0xC, 0xD):
+            i += 1
+        elif status >> 4 in (0x8, 0x9):
+            key, vel = (status & 0xF, data[i]), data[i + 1]
+            i += 2
+            if status >> 4 == 0x9 and vel > 0:
+                open_notes.setdefault(key, []).append(len(notes))
+                notes.append([now, None, key[1], vel])
+            elif open_notes.get(key):
+                notes[open_notes[key].pop(0)][1] = now
+        else:
+            i += 2
+        if i > end:                                                              # a length that points behind the chunk
+            raise IndexError(i)
+    return notes, now
 
 
 def decode_batch(mode, sequences, input_ids_mask_ori, batch_index, previous_count, output_dir, return_indices=False,

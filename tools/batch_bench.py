@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Throughput of the device batch producers / token validators at a BASELINE-sized batch
 (512 sequences, ~1000 tokens each), with the numpy oracle (= the reference's per-token Python loops restated) beside it; then
-the decode path (csrc/decode.hip) on 512 x 1024 generated rows beside its numpy restatement (profiles/decode_events.txt)."""
+the decode path (csrc/decode.hip) on 512 x 1024 generated rows beside its numpy restatement (profiles/decode_events.txt); then the
+encode path (csrc/encode.hip) on 512 rows of about 500 notes (profiles/encode_events.txt)."""
 import os
 import sys
 import time
@@ -105,3 +106,48 @@ print("%-18s %8.1f us" % ("mh_restore_chord", us_restore))
 print("%-18s %8.1f us" % ("mh_decode_events", us_events))
 print("%-18s %8.1f us  (allocation, zero fill and both kernels)   | numpy/python restatement, 1 core: %8.1f ms per batch (%.0fx the two kernels)"
       % ("decode_tokens", us_all, host_ms, host_ms * 1e3 / (us_restore + us_events)), flush=True)
+
+# ---- encode: notes + chord progression -> event words -> merged model rows (csrc/encode.hip), 512 rows of about 500 notes over 16
+# measures from the tests' generator (encode_ref.bench_items: every time signature, 480 / 96 / 220 / 384 ticks per beat), event-timed per
+# entry point, beside the numpy restatement on one core.  tools/make_golden_encode.py --time-reference times the reference itself on
+# the same rows where the reference is installed.  A single box's numbers; nothing gates on them.
+import encode_ref as er  # noqa: E402
+from musediffusion_amd.utils import encode_util as menc  # noqa: E402
+
+items = er.bench_items()
+p = er.pack(items)
+B, LD, S = len(items), 4096, 11
+d = {k: torch.from_numpy(a).cuda() for k, a in p.items()}
+words, wlen = torch.empty(B, LD, dtype=torch.int32, device="cuda"), torch.empty(B, dtype=torch.int32, device="cuda")
+ecounts, est = torch.empty(B, 2, dtype=torch.int32, device="cuda"), torch.empty(B, dtype=torch.int32, device="cuda")
+src = torch.randint(560, 729, (B, S), dtype=torch.int32, device="cuda")
+cap = B * (S + 1 + 2 * LD)
+ids, mask = torch.empty(cap, dtype=torch.int32, device="cuda"), torch.empty(cap, dtype=torch.int32, device="cuda")
+moff, mlen, mst = torch.empty(B + 1, dtype=torch.int64, device="cuda"), torch.empty(B, dtype=torch.int32, device="cuda"), torch.empty(B, dtype=torch.int32, device="cuda")
+
+
+def encode():
+    lib().mh_encode_events(d["notes"].data_ptr(), d["n_notes"].data_ptr(), d["params"].data_ptr(), d["slots"].data_ptr(), d["n_slots"].data_ptr(),
+                           words.data_ptr(), wlen.data_ptr(), ecounts.data_ptr(), est.data_ptr(), B, p["notes"].shape[1], p["slots"].shape[1], LD,
+                           current_stream())
+
+
+def merge():
+    lib().mh_merge_and_mask(src.data_ptr(), None, words.data_ptr(), wlen.data_ptr(), est.data_ptr(), ids.data_ptr(), mask.data_ptr(),
+                            moff.data_ptr(), mlen.data_ptr(), mst.data_ptr(), B, S, LD, cap, current_stream())
+
+
+us_encode, us_merge = timeit(encode), timeit(merge)
+us_py = timeit(lambda: menc.merge_and_mask(src, *(lambda e: (e.words, e.lengths, e.status))(menc.encode_notes(*(d[k] for k in ("notes", "n_notes", "params", "slots", "n_slots"))))))
+t0 = time.perf_counter()
+ref = er.encode_rows({k: a[:32] for k, a in p.items()}, LD)
+for w, _, _ in ref:
+    er.merge_row(np.zeros(S, np.int32), w)
+host_ms = (time.perf_counter() - t0) / 32 * B * 1e3
+torch.cuda.synchronize()
+assert [int(x) for x in est[:32].cpu()] == [r[2] for r in ref] and all(words[b, :len(r[0])].cpu().tolist() == r[0] for b, r in enumerate(ref))
+print("encode: %d rows, %d notes (%d rows encode, %d words, %d merged tokens)" % (B, int(p["n_notes"].sum()), int((est == 0).sum()), int(wlen.sum()), int(moff[-1])))
+print("%-18s %8.1f us" % ("mh_encode_events", us_encode))
+print("%-18s %8.1f us  (three launches)" % ("mh_merge_and_mask", us_merge))
+print("%-18s %8.1f us  (allocations and both entry points)   | numpy/python restatement, 1 core: %8.1f ms per batch (%.0fx the two entry points)"
+      % ("encode + merge (py)", us_py, host_ms, host_ms * 1e3 / (us_encode + us_merge)), flush=True)
