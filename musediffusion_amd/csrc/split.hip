@@ -54,6 +54,9 @@ template <> struct Sp<f16> {
   }
 };
 
+// the part type as the launch notes name it (dtype=): the recorder's kernel text shows `T` only
+template <typename T> constexpr const char* sp_name() { return std::is_same<T, bf16>::value ? "bf16x3" : "f16x3"; }
+
 template <typename T, int N>
 __device__ __forceinline__ void split(const float (&v)[N], T (&hi)[N], T (&lo)[N]) {
 #pragma unroll
@@ -603,7 +606,7 @@ int launch_gemm_ln(const SpGemmArgs& g, const float* gamma, const float* beta, f
   MH_CHECK_ARG((int64_t)(g.K / 16) * g.lda * 64 < (1ll << 31) && (int64_t)(g.K / 16) * g.ldw * 64 < (1ll << 31),
                "split_gemm_res_ln: an operand beyond 2 GiB (K=%d lda=%lld ldw=%lld): buffer-descriptor addressing is 32-bit", g.K, (long long)g.lda, (long long)g.ldw);
   const dim3 grid((unsigned)((g.M + RBM - 1) / RBM)), block(512);
-  mh_prof_note("split tile=128x512 +LN M=%lld N=%d K=3x%d", (long long)g.M, g.N, g.K);
+  mh_prof_note("split tile=128x512 +LN M=%lld N=%d K=3x%d dtype=%s", (long long)g.M, g.N, g.K, sp_name<T>());
   MH_LAUNCH((split_gemm_ln_kernel<T>), grid, block, 0, s, g, gamma, beta, eps);
   MH_CHECK_LAUNCH();
   return MH_OK;
@@ -629,7 +632,8 @@ int launch_gemm(const SpGemmArgs& g0, int act, hipStream_t s) {
   g.ntiles = (int)tiles;
   const int64_t slots = 2 * (int64_t)sp_device_cus();
   const dim3 grid((unsigned)(tiles < slots ? tiles : slots)), block(256);
-  mh_prof_note("split tile=256x128 act=%d M=%lld N=%d K=3x%d out=%d", act, (long long)g.M, g.N, g.K, g.out_mode);
+  mh_prof_note("split tile=256x128 act=%d M=%lld N=%d K=3x%d out=%d dtype=%s bias=%s res=%d nt=%d ntiles=%d", act, (long long)g.M, g.N, g.K, g.out_mode,
+               sp_name<T>(), !g.bias ? "0" : (g.bias_rows ? "row" : "col"), g.res ? 1 : 0, g.stream_out, g.ntiles);
   switch (act) {
     case MH_ACT_NONE: MH_LAUNCH((split_gemm_kernel<T, MH_ACT_NONE>), grid, block, 0, s, g); break;
     case MH_ACT_TANH: MH_LAUNCH((split_gemm_kernel<T, MH_ACT_TANH>), grid, block, 0, s, g); break;
@@ -869,7 +873,7 @@ int launch_attn(const void* qk, int64_t ldq, int koff, int64_t qk_part, const vo
                 int nh, int dh, float scale, hipStream_t s) {
   const float sl2 = scale * 1.4426950408889634f;
   const int H = nh * dh;
-  mh_prof_note("split attention B=%d L=%d nh=%d dh=%d", B, L, nh, dh);
+  mh_prof_note("split attention B=%d L=%d nh=%d dh=%d dtype=%s", B, L, nh, dh, sp_name<T>());
   if (dh == 64 && L >= 256) {   // eight waves: 256 queries per block
     const dim3 grid8((unsigned)((L + 255) / 256), (unsigned)(B * nh)), block8(512);
     MH_LAUNCH((split_attn_kernel<T, 64, 8>), grid8, block8, 0, s, (const T*)qk, ldq, koff, qk_part, (const T*)vt, ldv, vt_part, (T*)ctx, ld_ctx, H, L, nh, sl2);
@@ -901,6 +905,7 @@ namespace {
 template <typename T>
 int pack_impl(const float* x, int64_t ldx, void* out, int64_t ld, int64_t rows, int cols, int kpad, hipStream_t s) {
   const dim3 grid((unsigned)((rows + 63) / 64), (unsigned)(kpad / 32)), block(256);
+  mh_prof_note("split pack rows=%lld cols=%d pad=%d dtype=%s", (long long)rows, cols, kpad, sp_name<T>());
   MH_LAUNCH((split_pack_kernel<T>), grid, block, 0, s, x, ldx, (T*)out, ld, rows, cols, kpad);
   MH_CHECK_LAUNCH();
   return MH_OK;
@@ -908,6 +913,7 @@ int pack_impl(const float* x, int64_t ldx, void* out, int64_t ld, int64_t rows, 
 template <typename T>
 int join_impl(const void* in, int64_t ld, float* out, int64_t ldo, int64_t rows, int cols, int cpad, hipStream_t s) {
   const dim3 grid((unsigned)((rows + 63) / 64), (unsigned)(cpad / 32)), block(256);
+  mh_prof_note("split join rows=%lld cols=%d pad=%d dtype=%s", (long long)rows, cols, cpad, sp_name<T>());
   MH_LAUNCH((split_join_kernel<T>), grid, block, 0, s, (const T*)in, ld, cpad / 32, out, ldo, rows, cols);
   MH_CHECK_LAUNCH();
   return MH_OK;
@@ -916,6 +922,7 @@ template <typename T>
 int ln_impl(const float* x, int64_t ldx, const float* pos, const float* emb_t, const int32_t* emb_row, const float* gamma, const float* beta, void* out,
             int64_t ld, int64_t rows, int L, int H, float eps, hipStream_t s) {
   const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+  mh_prof_note("split layernorm add=%d H=%d rows=%lld dtype=%s", pos ? 1 : 0, H, (long long)rows, sp_name<T>());
   if (pos) MH_LAUNCH((split_ln_kernel<T, true>), grid, block, 0, s, x, ldx, pos, emb_t, emb_row, gamma, beta, (T*)out, ld, rows, L, H, eps);
   else MH_LAUNCH((split_ln_kernel<T, false>), grid, block, 0, s, x, ldx, pos, emb_t, emb_row, gamma, beta, (T*)out, ld, rows, L, H, eps);
   MH_CHECK_LAUNCH();
