@@ -7,10 +7,11 @@ import ctypes as C
 
 import torch
 
-from ._lib import MH_BF16, MH_BF16X3, MH_F16X3, MH_F32, check, current_stream, lib, ptr, require_device
+from ._lib import (ACT_GELU_ERF, ACT_NONE, ACT_SILU, ACT_TANH, MH_BF16, MH_BF16X3, MH_F16X3, MH_F32, check, current_stream, lib, ptr,
+                   require_device)
 
 TORCH_DTYPE = {MH_F32: torch.float32, MH_BF16: torch.bfloat16}
-ACT = {None: 0, "none": 0, "tanh": 1, "gelu": 2, "silu": 3}
+ACT = {None: ACT_NONE, "none": ACT_NONE, "tanh": ACT_TANH, "gelu": ACT_GELU_ERF, "silu": ACT_SILU}
 
 
 SPLIT_DTYPES = (MH_BF16X3, MH_F16X3)   # split precision (csrc/split.hip): the denoiser forward only

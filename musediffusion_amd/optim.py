@@ -19,6 +19,9 @@ from . import _lib
 from ._lib import OptHParams, check, current_stream, lib, ptr
 
 CHUNK = 1 << 16
+# host images of the device tables: one mh_opt_chunk per chunk, one mh_opt_tensor (8 pointers) per parameter
+CHUNK_DTYPE = np.dtype([("tensor", "<i4"), ("count", "<i4"), ("offset", "<i8")])
+TENSOR_ROW = 8   # int64 words: param, grad, exp_avg, exp_avg_sq, ema[4]
 
 
 class FusedAdamWEMA:
@@ -44,7 +47,7 @@ class FusedAdamWEMA:
             n = p.numel()
             for off in range(0, n, CHUNK):
                 chunks.append((i, min(CHUNK, n - off), off))
-        arr = np.zeros(len(chunks), dtype=[("tensor", "<i4"), ("count", "<i4"), ("offset", "<i8")])
+        arr = np.zeros(len(chunks), dtype=CHUNK_DTYPE)
         for k, (i, c, o) in enumerate(chunks):
             arr[k] = (i, c, o)
         self.n_chunks = len(chunks)
@@ -75,7 +78,7 @@ class FusedAdamWEMA:
                 self.params[i].grad = grads[i] = g.clone()
         key = tuple(0 if g is None else g.data_ptr() for g in grads)
         if self._table is None or key != self._table_key:
-            rows = np.zeros((len(self.params), 8), dtype=np.int64)
+            rows = np.zeros((len(self.params), TENSOR_ROW), dtype=np.int64)
             for i, p in enumerate(self.params):
                 g = grads[i]
                 rows[i, 0], rows[i, 1] = p.data_ptr(), 0 if g is None else g.data_ptr()

@@ -19,7 +19,7 @@ import torch
 from torch.autograd import Function
 
 from . import _lib, ops
-from ._lib import MH_F32, check, current_stream, lib, ptr
+from ._lib import ACT_DERIV, MH_F32, check, current_stream, lib, ptr
 
 NPART = 256  # rows of the two-stage column-sum scratch
 TN_DW = True            # bf16: weight gradients straight from the k-major activations (mh_gemm_dw), no transposed copies
@@ -27,7 +27,6 @@ FUSED_FFN = True        # bf16: FFN as one tape node with the GELU backward fuse
 FUSED_ATTENTION = True  # bf16: streaming forward + fused backward kernels when the shape allows (A/B switch for tests)
 LN_BWD_DROP = True           # the LayerNorm backward also writes its input gradient x the dense node's dropout mask (mh_layernorm_bwd_drop)
 GELU_DERIV_FWD = True        # the FFN node keeps gelu'(pre) instead of pre (mh_gemm_bias_act_dact; A/B: tools/ab_train.py GELU_DERIV_FWD)
-ACT_DERIV = 4                # MH_ACT_DERIV
 WEIGHT_PREP = True      # bf16: the encoder's weight casts / transposes of a forward + backward in one launch (_WeightPrep)
 FUSED_DENSE_LN = True   # bf16, d_model 512: BertSelfOutput / BertOutput dense -> dropout -> + input -> LayerNorm as one kernel
 # round 5: the fused q | k | v projection as tape-only stacking of its three parameters (no fp32 torch.cat per layer and step, one bias pack per

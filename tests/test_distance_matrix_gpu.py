@@ -26,12 +26,11 @@ import distance_ref as dr
 pytestmark = pytest.mark.gpu
 
 from musediffusion_amd import ops, training  # noqa: E402
-from musediffusion_amd._lib import MH_F32, check, current_stream, lib, ptr  # noqa: E402
+from musediffusion_amd._lib import MH_ERR_INVALID, MH_F32, check, current_stream, lib, ptr  # noqa: E402
 
 DEV = "cuda"
 NAN = float("nan")
 SLACK = 256
-MH_ERR_INVALID = -1      # include/musehip.h, enum mh_status
 CASES = [(V, ld, E) for V, ld in dr.VS for E in dr.ES]
 
 

@@ -11,21 +11,14 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 from musediffusion_amd import _lib  # noqa: E402
 
 
-class mh_dropout(ctypes.Structure):
-    _fields_ = [("p", ctypes.c_float), ("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64), ("mask", ctypes.c_void_p)]
-
-
 new = _lib.lib()
 old = ctypes.CDLL(os.path.abspath(sys.argv[1]))
-for L_ in (new, old):
-    L_.mh_dropout_bits.restype = ctypes.c_int
-    L_.mh_dropout_bits.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(mh_dropout), ctypes.c_void_p]
-    L_.mh_dropout_bits_words.restype = ctypes.c_size_t
-    L_.mh_dropout_bits_words.argtypes = [ctypes.c_int, ctypes.c_int]
+for name in ("mh_dropout_bits", "mh_dropout_bits_words"):
+    getattr(old, name).restype, getattr(old, name).argtypes = _lib.SIGNATURES[name]
 stream = torch.cuda.current_stream().cuda_stream
 for BH, L, p in ((256, 1024, 0.1), (6, 528, 0.1), (4, 100, 0.37), (3, 64, 0.999), (5, 96, 0.00390625), (2, 2096, 0.25)):
     n = new.mh_dropout_bits_words(BH, L)
-    d = mh_dropout(p, 0x1234567887654321, (7 << 16) | 3, None)
+    d = _lib.Dropout(p, 0x1234567887654321, (7 << 16) | 3, None)
     a = torch.zeros(n, dtype=torch.int32, device="cuda")
     b = torch.zeros(n, dtype=torch.int32, device="cuda")
     assert new.mh_dropout_bits(a.data_ptr(), BH, L, ctypes.byref(d), stream) == 0
