@@ -17,7 +17,7 @@
 // One swizzle serves both kinds of read (row_swz).  The fragments of a 32-row sub-tile are read ahead of the MFMAs that
 // use them: the next sub-tile's row fragments and this one's transposed fragments land under the exp / dS vector work.
 // Recomputing S in both kernels costs 2 extra products but needs neither atomics nor an [L, L] tensor in HBM.
-#include "common.h"
+#include "lds_dma.h"
 
 namespace {
 
@@ -26,10 +26,6 @@ namespace {
 #endif
 constexpr int SKB = MH_BWD_SKB;   // rows (keys or queries) per LDS stage: 128 or 256 (build-time A/B: -DMH_BWD_SKB=256)
 static_assert(SKB == 128 || SKB == 256, "stage of 128 or 256 rows");
-
-__device__ __forceinline__ void glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
 
 // 16-byte chunk c of row r of a row-layout stage ([row][DH] bf16) is stored at chunk c ^ row_swz(r).
 // dh 64 (128-byte rows, two per 256 bytes of banks): a rotation of (r >> 1) & 7 - any bijection of those three bits keeps the
@@ -48,7 +44,7 @@ __device__ __forceinline__ void dma_rows(const bf16* src, int64_t ld, char* dst,
   const int row = p * KRP + lane / CH, pc = lane % CH;
   const int lc = pc ^ row_swz<DH>(row);
   const int rsrc = row < valid_rows ? row : valid_rows - 1;     // rows past the sequence end: a valid row (their terms are masked)
-  glds16(src + (int64_t)rsrc * ld + lc * 8, dst + p * 1024);
+  mh_glds16(src + (int64_t)rsrc * ld + lc * 8, dst + p * 1024);
 }
 // where the [L, dh] rows of one (batch, head) live: [B, nh, L, dh] tensors or column blocks of token-major [B L, ld] ones
 struct RowLayout {
@@ -144,7 +140,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(const bf16* __restrict
     if constexpr (DROP && FULL) {   // this wave's keep words of the stage's two 64-key tiles (2 x 64 words, contiguous): 512 B, lanes 0..31
       const int qbw = (item % nqb) * 8 + wave;
       if (lane < KWW / 16)
-        glds16(keep_bits + drop_word_index(bh, (L + 31) >> 5, qbw, st * (SKB / 64), 0) + 4 * lane, smem_dyn + 2 * 2 * ST + (g & 1) * KWB + wave * KWW);
+        mh_glds16(keep_bits + drop_word_index(bh, (L + 31) >> 5, qbw, st * (SKB / 64), 0) + 4 * lane, smem_dyn + 2 * 2 * ST + (g & 1) * KWB + wave * KWW);
     }
   };
 
@@ -276,7 +272,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(const bf16* __restrict
         }
       }
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    mh_wait_lgkmcnt0_fence();
 #ifdef MH_BWD_PROF
     {   // debug build (tools/debug/bwd_prof.py): per (block, wave) clocks spent waiting for the DMA, at the top barrier, in the stage, at the end barrier
       const unsigned long long tp3 = __builtin_amdgcn_s_memtime();
@@ -337,18 +333,18 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(const bf16* __restric
       if (wave == 0) {   // lanes 0-31: lse2 of the 128 queries, lanes 32-63: D (groups of 4; past the end: the last valid group)
         int qo = 4 * (lane & 31);
         if (qo >= valid) qo = valid - 4;
-        glds16((lane < 32 ? lse2 : Dv) + r0 + qo, base + 2 * ST);
+        mh_glds16((lane < 32 ? lse2 : Dv) + r0 + qo, base + 2 * ST);
       }
     } else {
       if (wave < 2) {    // wave 0: lse2 of the 256 queries, wave 1: D
         int qo = 4 * lane;
         if (qo >= valid) qo = valid - 4;
-        glds16((wave == 0 ? lse2 : Dv) + r0 + qo, base + 2 * ST + wave * 1024);
+        mh_glds16((wave == 0 ? lse2 : Dv) + r0 + qo, base + 2 * ST + wave * 1024);
       }
     }
     if constexpr (DROP && FULL) {   // keep words of (the stage's 32-query blocks) x (the block's 4 pairs of key blocks): 1 KiB per query block
       if (wave >= NW - KWQ)
-        glds16(keep_bits + drop_word_index(bh, (L + 31) >> 5, st * KWQ + wave - (NW - KWQ), (item % nkb) * 4, 0) + 4 * lane,
+        mh_glds16(keep_bits + drop_word_index(bh, (L + 31) >> 5, st * KWQ + wave - (NW - KWQ), (item % nkb) * 4, 0) + 4 * lane,
                base + 2 * ST + LSTB + (wave - (NW - KWQ)) * 1024);
     }
   };
@@ -490,7 +486,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(const bf16* __restric
         }
       }
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    mh_wait_lgkmcnt0_fence();
     __builtin_amdgcn_s_barrier();
   }
 }
@@ -525,8 +521,7 @@ int launch_bwd(const bf16* q, const bf16* k, const bf16* v, const bf16* dO, cons
   constexpr int bytes_dq = 2 * 2 * ST + (DROP && FULL ? 2 * 8 * (SKB / 64) * 256 : 0), bytes_dkv = 2 * (2 * ST + 2 * SKB * 4 + (DROP && FULL ? (SKB / 32) * 1024 : 0));
   if (int rc = mh_allow_dynamic_lds((const void*)&attn_bwd_dq_kernel<DH, DROP, FULL>, bytes_dq)) return rc;
   if (int rc = mh_allow_dynamic_lds((const void*)&attn_bwd_dkv_kernel<DH, DROP, FULL>, bytes_dkv)) return rc;
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+  const int cus = mh_device_cus();
   const int nbh = B * nh, nitems = nbh * ((L + 255) / 256);
   const dim3 grid((unsigned)(nitems < cus ? nitems : cus)), block(512);
   const float sl2 = scale * 1.4426950408889634f;

@@ -90,8 +90,7 @@ int stream_fwd_impl(const void* q, const void* k, const void* vt_perm, void* ctx
   MH_CHECK_ARG(ctx_panel || ld_ctx % 4 == 0, "attention_stream: ld_ctx must be a multiple of 4");
   MH_CHECK_ARG(!pre || mh_attention_stream_prescaled_supported(L, dh), "attention_stream(pre-scaled): seq_len %d must be a multiple of 256", L);
   hipStream_t s = (hipStream_t)stream;
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+  const int cus = mh_device_cus();
   const int nbh = B * nh;
   const float sl2 = scale * 1.4426950408889634f;
   const bf16 *Q = (const bf16*)q, *K = (const bf16*)k, *V = (const bf16*)vt_perm;

@@ -2,7 +2,7 @@
 // which lists every instantiation once (the product's there, the debug library's remainder in attn_stream_dbg.h), so no kernel is
 // instantiated in two objects.  The kernel has INTERNAL linkage: no other object names it.
 #pragma once
-#include "common.h"
+#include "lds_dma.h"
 
 namespace {
 
@@ -75,8 +75,7 @@ __global__ __launch_bounds__(64 * NW) void attn_stream_bf16_kernel(const bf16* _
       const int lc = pc ^ ((row / RPB) & (CH - 1));
       int rsrc = row;                                                   // keys past the end: any valid row (their scores are masked)
       if (!FULL && st * SK + row >= L) rsrc = L - 1 - st * SK;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(Kb + (int64_t)rsrc * qld + lc * 8),
-                                       (__attribute__((address_space(3))) void*)(kdst + p * 1024), 16, 0, KVNT ? 2 : 0);
+      mh_glds16<KVNT ? 2 : 0>(Kb + (int64_t)rsrc * qld + lc * 8, kdst + p * 1024);
     }
 #pragma unroll
     for (int j = 0; j < PK; ++j) {
@@ -85,8 +84,7 @@ __global__ __launch_bounds__(64 * NW) void attn_stream_bf16_kernel(const bf16* _
       const int lc = pc ^ ((d >> 1) & 7);
       int kc = t * 64 + lc * 8;                                         // 8 keys past the end: any valid chunk (finite values x P = 0)
       if (!FULL && st * SK + kc >= L) kc = L - 8 - st * SK;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(Vb + (int64_t)d * L + kc),
-                                       (__attribute__((address_space(3))) void*)(vdst + p * 1024), 16, 0, KVNT ? 2 : 0);
+      mh_glds16<KVNT ? 2 : 0>(Vb + (int64_t)d * L + kc, vdst + p * 1024);
     }
   };
 
@@ -363,7 +361,7 @@ __global__ __launch_bounds__(64 * NW) void attn_stream_bf16_kernel(const bf16* _
         }
       }
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    mh_wait_lgkmcnt0_fence();
     if constexpr ((ABL & 128) != 0) {
       const unsigned long long tp3 = __builtin_amdgcn_s_memtime();
       __builtin_amdgcn_s_barrier();

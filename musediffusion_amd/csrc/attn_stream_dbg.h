@@ -37,16 +37,14 @@ __global__ __launch_bounds__(512, 2) void attn_stream2_kernel(const bf16* __rest
       const int p = wave + NW * j;
       const int row = p * KRP + lane / CH, pc = lane % CH;
       const int lc = pc ^ ((row / RPB) & (CH - 1));
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(Kb + (int64_t)row * qld + lc * 8),
-                                       (__attribute__((address_space(3))) void*)(kdst + p * 1024), 16, 0, KVNT ? 2 : 0);
+      mh_glds16<KVNT ? 2 : 0>(Kb + (int64_t)row * qld + lc * 8, kdst + p * 1024);
     }
 #pragma unroll
     for (int j = 0; j < PK; ++j) {
       const int p = wave + NW * j;
       const int t = p / (DH / 8), d = (p % (DH / 8)) * 8 + (lane >> 3), pc = lane & 7;
       const int lc = pc ^ ((d >> 1) & 7);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(Vb + (int64_t)d * L + t * 64 + lc * 8),
-                                       (__attribute__((address_space(3))) void*)(vdst + p * 1024), 16, 0, KVNT ? 2 : 0);
+      mh_glds16<KVNT ? 2 : 0>(Vb + (int64_t)d * L + t * 64 + lc * 8, vdst + p * 1024);
     }
   };
   const int ksw0 = (lq / RPB) & (CH - 1), ksw1 = ((32 + lq) / RPB) & (CH - 1);
@@ -175,7 +173,7 @@ __global__ __launch_bounds__(512, 2) void attn_stream2_kernel(const bf16* __rest
         }
       }
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    mh_wait_lgkmcnt0_fence();
     __builtin_amdgcn_s_barrier();                      // every wave is done reading buffer g & 1
   }
 }

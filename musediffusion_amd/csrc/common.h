@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
 #include <mutex>
 #include <set>
 #include <utility>
@@ -91,6 +92,22 @@ static inline int mh_allow_dynamic_lds(const void* kernel, size_t bytes) {
   done.insert(key);
   return MH_OK;
 }
+
+// Compute units of the CURRENT device, asked of the runtime once per device (the library may serve several devices from one process and be
+// called from several host threads: a slot is written once, with the same value whoever fills it).  ONE cache per library, not per object.
+__attribute__((visibility("hidden"))) inline int mh_device_cus() {
+  static std::atomic<int> cus[MH_MAX_DEVICES];   // (static storage: zeros = not asked yet)
+  const int dev = mh_current_device();
+  int n = cus[dev].load(std::memory_order_relaxed);
+  if (n == 0) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    cus[dev].store(n, std::memory_order_relaxed);
+  }
+  return n;
+}
+// A K32-panel operand ([npanels][ld rows][32] 2-byte elements) that a buffer descriptor can address (lds_dma.h, mh_panel_rsrc): its byte count is
+// a 31-bit number
+static inline bool mh_panel_desc_fits(int64_t npanels, int64_t ld) { return npanels * ld * 64 < (1ll << 31); }
 
 // ---- scalar conversions.  Plain casts: hipcc emits v_cvt_pk_bf16_f32 (RNE, NaN-preserving).
 __device__ __forceinline__ float to_f32(float v) { return v; }

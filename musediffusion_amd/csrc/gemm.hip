@@ -37,7 +37,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmArgs g) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int tiles_n = (g.N + BN - 1) / BN;
-  const int bid = xcd_remap(blockIdx.x, gridDim.x);
+  const int bid = mh_xcd_remap(blockIdx.x, gridDim.x);
   const int64_t m0 = (int64_t)(bid / tiles_n) * BM;
   const int n0 = (bid % tiles_n) * BN;
   const T* __restrict__ A = reinterpret_cast<const T*>(g.A) + (int64_t)blockIdx.y * g.sA;
@@ -281,17 +281,6 @@ MH_KNOB(int, g_variant, 2);  // bf16 kernel choice: 0 the 128x128 register-stage
 
 namespace mhgemm __attribute__((visibility("hidden"))) {
 
-// compute units of the CURRENT device (cached per device: the library may serve several devices from one process)
-int device_cus() {
-  static int cus[MH_MAX_DEVICES] = {};
-  const int dev = mh_current_device();
-  if (!cus[dev]) {
-    int n = 0;
-    cus[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-  }
-  return cus[dev];
-}
-
 bool big_tile_ok(const GemmArgs& g) {
   // N % 8 == 0: a lane's 8 output columns are all valid; an fp32 row-major output may end on a half group (N % 4 == 0, e.g. the
   // released checkpoints' E = 500 down-projection): the epilogue stores only the first four of the last lane's columns
@@ -320,7 +309,7 @@ bool want_wide(const GemmArgs& g, int batch) {
   }
   if (g_variant != 2 || !g_auto_wide || batch != 1) return false;
   if (g.a_panel || g.w_panel || g.o_panel || g.r_panel || g.q) return false;
-  return (int64_t)ceil_div(g.M, 256) * (g.N / 256) >= device_cus();
+  return (int64_t)ceil_div(g.M, 256) * (g.N / 256) >= mh_device_cus();
 }
 
 // round 6: dense + bias + GELU of K32 panels (the sampler's FFN1) on the column-strip kernel; A/B: mh_gemm_set_strip(0) = gemm_big_kernel

@@ -1,5 +1,5 @@
-// gemm_args.h - what the GEMM objects share: the kernel argument structs, the big-tile configurations, four small device helpers and the
-// host functions that cross an object boundary.
+// gemm_args.h - what the GEMM objects share: the kernel argument structs, the big-tile configurations, apply_act and the host functions
+// that cross an object boundary (the stage-DMA, wait-count and descriptor idioms: lds_dma.h).
 //   gemm.hip           entry points, the dispatcher launch<EPI>, the 128x128 kernel (gemm_kernel), the nearest-embedding score path
 //   gemm_big.h         the big-tile kernel (gemm_big_kernel) and launch_big<Cfg, EPI>, explicitly instantiated - once each - by
 //   gemm_big_std.hip   256x128, EPI 0      gemm_big_wide.hip  256x256, EPI 0
@@ -11,7 +11,7 @@
 #pragma once
 #include <type_traits>
 
-#include "common.h"
+#include "lds_dma.h"
 
 int mh_drop_args(const mh_dropout* d, DropArgs* out);   // dropout.hip
 
@@ -72,24 +72,6 @@ __device__ __forceinline__ float apply_act(float v, int act) {
   }
 }
 
-// XCD-aware block remap (8 XCDs, blocks dealt round-robin): give each XCD a contiguous run of
-// tiles so the A row-panel a run shares stays in that XCD's L2.  Bijective for any grid size.
-__device__ __forceinline__ int xcd_remap(int bid, int nblk) {
-  const int q = nblk >> 3, r = nblk & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
-
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-// wait until all but the youngest `stages` DMA stages (PIECES loads each) of this wave have landed; EXTRA = vector-memory
-// operations of another kind (the previous tile's epilogue stores) issued after the awaited stage (vmcnt counts in issue order)
-template <int PIECES, int EXTRA = 0> __device__ __forceinline__ void wait_stages(int stages) {
-  static_assert(3 * PIECES + EXTRA <= 63, "vmcnt is a 6-bit counter");
-  if (stages >= 3) wait_vmcnt<3 * PIECES + EXTRA>();
-  else if (stages == 2) wait_vmcnt<2 * PIECES + EXTRA>();
-  else if (stages == 1) wait_vmcnt<PIECES + EXTRA>();
-  else wait_vmcnt<EXTRA>();
-}
-
 // Big-tile configurations (gemm_big.h describes the kernels)
 template <int BM_, int BN_, int WM_, int WN_, int NST_, bool PP_ = false>
 struct BigCfg {
@@ -123,7 +105,6 @@ inline MH_KNOB(int, g_buf_dma, 1);
 inline MH_KNOB(int, g_plain_stores, MH_PLAIN_STORES_DEFAULT);   // A/B: bit 0 QKV streaming instead of ordinary stores, bit 1 dense+GELU ordinary instead of streaming stores; bit 2: full-row tile without ping-pong; bits 3 / 4: 64-row full-row tile
 
 // ---- host functions defined in one object and called from another
-int device_cus();                          // gemm.hip: compute units of the current device
 bool big_tile_ok(const GemmArgs& g);       // gemm.hip
 template <class C, int EPI> int launch_big(const GemmArgs& g0, hipStream_t s, int batch);   // gemm_big.h; instantiated by gemm_big_*.hip
 bool strip_ok(const GemmArgs& g);          // gemm_strip.h (gemm_big_std.hip)

@@ -60,11 +60,11 @@ __device__ __forceinline__ void issue_stage_buf(const char* smem, const BufDma& 
   static_for<0, C::PA>([&](auto jc) {
     constexpr int j = decltype(jc)::value;
     // (the instruction's immediate offset advances the LDS address as well as the buffer address: every piece names the FIRST piece's slot)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(b.ra, (__attribute__((address_space(3))) void*)(base + ldsA[0]), 16, b.va, kt * b.ka, j * 1024, AUX_A);
+    mh_buf_lds16<j * 1024, AUX_A>(b.ra, base + ldsA[0], b.va, kt * b.ka);
   });
   static_for<0, C::PW>([&](auto jc) {
     constexpr int j = decltype(jc)::value;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(b.rw, (__attribute__((address_space(3))) void*)(base + C::BM * 64 + ldsW[0]), 16, b.vw, kt * b.kw, j * 1024, 0);
+    mh_buf_lds16<j * 1024>(b.rw, base + C::BM * 64 + ldsW[0], b.vw, kt * b.kw);
   });
 }
 
@@ -76,18 +76,12 @@ __device__ __forceinline__ void issue_stage(const char* smem, const char* const 
   char* base = const_cast<char*>(smem) + (kt % C::NST) * C::STAGE;
 #pragma unroll
   for (int j = 0; j < C::PA; ++j) {
-    if constexpr (C::PP)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcA[j] + kt * kstepA),
-                                       (__attribute__((address_space(3))) void*)(base + ldsA[j]), 16, 0, MH_PP_A_AUX);
-    else
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcA[j] + kt * kstepA),
-                                       (__attribute__((address_space(3))) void*)(base + ldsA[j]), 16, 0, 0);
+    mh_glds16<C::PP ? MH_PP_A_AUX : 0>(srcA[j] + kt * kstepA, base + ldsA[j]);
   }
   if constexpr ((DBG & 4096) != 0) return;   // timing-only ablation: the W pieces are not issued (what their issue costs the loop)
 #pragma unroll
   for (int j = 0; j < C::PW; ++j)
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcW[j] + kt * kstepW),
-                                     (__attribute__((address_space(3))) void*)(base + C::BM * 64 + ldsW[j]), 16, 0, 0);
+    mh_glds16(srcW[j] + kt * kstepW, base + C::BM * 64 + ldsW[j]);
 }
 
 // Main loop.  Fragments of K-step kt live in registers while its MFMAs run; the fragments of kt+1 are read
@@ -121,12 +115,12 @@ __device__ __forceinline__ void big_mainloop(f32x4 (&acc)[C::TI][C::TJ], const c
   const int npro = nk < C::NST ? nk : C::NST;
   constexpr bool COUNTED = NSTORE > 0 && (C::NST - 1) * NPIECES + NSTORE <= 63;
   if (pre == 2 && COUNTED) {
-    wait_stages<NPIECES, COUNTED ? NSTORE : 0>(npro - 1);   // stage 0 landed; stages 1.. and the stores stay in flight
+    mh_wait_stages<NPIECES, COUNTED ? NSTORE : 0>(npro - 1);   // stage 0 landed; stages 1.. and the stores stay in flight
   } else if (pre) {   // the stages were issued before the previous tile's epilogue, whose stores share the counter: drain all
-    wait_vmcnt<0>();
+    mh_wait_vmcnt<0>();
   } else {
     for (int st = 0; st < npro; ++st) issue(st);
-    wait_stages<NPIECES>(npro - 1);
+    mh_wait_stages<NPIECES>(npro - 1);
   }
   __builtin_amdgcn_s_barrier();
   bf16x8 a[TI], b[TJ];
@@ -159,9 +153,9 @@ __device__ __forceinline__ void big_mainloop(f32x4 (&acc)[C::TI][C::TJ], const c
     pt0 = tick();
     if (kt > 0) pt_work += pt0 - pt1;
     // stage kt+1 was prefetched before the stores for kt + 1 < NST: the stores are younger than it
-    if (pre == 2 && COUNTED && kt + 1 < C::NST) wait_stages<NPIECES, COUNTED ? NSTORE : 0>(younger);
-    else wait_stages<NPIECES>(younger);
-    __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0)
+    if (pre == 2 && COUNTED && kt + 1 < C::NST) mh_wait_stages<NPIECES, COUNTED ? NSTORE : 0>(younger);
+    else mh_wait_stages<NPIECES>(younger);
+    mh_wait_lgkmcnt0();   // lgkmcnt(0)
     pt1 = tick();
     pt_wait += pt1 - pt0;
     __builtin_amdgcn_s_barrier();
@@ -219,10 +213,10 @@ __device__ __forceinline__ void pp_mainloop(f32x4 (&acc)[C::TI][C::TJ], const ch
   };
   const int npro = nk < D ? nk : D;
   if (pre) {
-    wait_vmcnt<0>();
+    mh_wait_vmcnt<0>();
   } else {
     for (int st = 0; st < npro; ++st) issue(st);
-    wait_stages<C::PIECES>(npro - 1);
+    mh_wait_stages<C::PIECES>(npro - 1);
   }
   __builtin_amdgcn_s_barrier();
   if (group == 1) __builtin_amdgcn_s_barrier();
@@ -237,8 +231,8 @@ __device__ __forceinline__ void pp_mainloop(f32x4 (&acc)[C::TI][C::TJ], const ch
 #pragma unroll
     for (int i = 0; i < TI; ++i) a[i] = read_frag(As + a_off + i * (16 * 64));
     if (kt + D < nk) issue(kt + D);
-    if (group == 1 && kt + 1 < nk) wait_stages<C::PIECES>(younger);
-    __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): fragments in registers, ring slot released
+    if (group == 1 && kt + 1 < nk) mh_wait_stages<C::PIECES>(younger);
+    mh_wait_lgkmcnt0();   // lgkmcnt(0): fragments in registers, ring slot released
     __builtin_amdgcn_s_barrier();
     // ---- MFMA(kt)
     __builtin_amdgcn_s_setprio(1);
@@ -257,7 +251,7 @@ __device__ __forceinline__ void pp_mainloop(f32x4 (&acc)[C::TI][C::TJ], const ch
       }
     }
     __builtin_amdgcn_s_setprio(0);
-    if (group == 0 && kt + 1 < nk) wait_stages<C::PIECES>(younger);
+    if (group == 0 && kt + 1 < nk) mh_wait_stages<C::PIECES>(younger);
     __builtin_amdgcn_s_barrier();
   }
   if (group == 0) __builtin_amdgcn_s_barrier();
@@ -305,7 +299,6 @@ __global__ __launch_bounds__(C::THREADS, C::STAGE * C::NST <= 80 * 1024 ? 2 : 1)
   const int tiles_n = (g.N + C::BN - 1) / C::BN;
   const int nk = g.K / B2K;
   const int fr = lane & 15, fg = lane >> 4;
-  constexpr int GSW[4] = {0, 2, 3, 1};
   // DMA coordinates: one piece covers 16 rows x 64 B; lane i lands at row i/4, physical chunk i%4.
   // row-major operand: rows ld elements apart, a K-step advances 32 elements; K32-panel operand
   // ([K/32][ld rows][32]): rows 32 elements apart, a K-step advances one whole panel (ld * 32)
@@ -323,27 +316,26 @@ __global__ __launch_bounds__(C::THREADS, C::STAGE * C::NST <= 80 * 1024 ? 2 : 1)
                 "buffer DMA: a wave's pieces of a stage must be consecutive (immediate offsets of 1 KiB, 12 bits)");
   BufDma bd;
   if constexpr (BUFDMA) {
-    const int rl = lane >> 2, lc = (lane & 3) ^ GSW[(rl >> 2) & 3];
+    const int rl = lane >> 2, lc = (lane & 3) ^ MH_GSW[(rl >> 2) & 3];
     bd.va = (((wave * C::PA) % C::APIECES) * 16 + rl) * 64 + lc * 16;
     bd.vw = ((wave * C::PW) * 16 + rl) * 64 + lc * 16;
     bd.ka = (int)(g.lda * 64);
     bd.kw = (int)(g.ldw * 64);
   }
   auto set_sources = [&](int tile) {
-    const int b2 = xcd_remap(tile, g.ntiles);
+    const int b2 = mh_xcd_remap(tile, g.ntiles);
     const int64_t tm0 = (int64_t)(b2 / tiles_n) * C::BM;
     const int tn0 = (b2 % tiles_n) * C::BN;
     if constexpr (BUFDMA) {   // (panel operands: row r of panel 0 at byte 64 r; everything here is wave-uniform)
       const int64_t offA = ((int64_t)blockIdx.y * g.sA) * 2 + tm0 * 64, offW = ((int64_t)blockIdx.y * g.sW) * 2 + (int64_t)tn0 * 64;
-      // bound = the rows this operand OWNS in its last panel (g.A may be a row window of a larger panel buffer: lda > M, first row > 0): rows
-      // beyond M / N of the last panel are zero-filled by the descriptor instead of being fetched from behind the allocation
+      // the bound of mh_panel_rsrc (lds_dma.h: the rows this operand OWNS in its last panel), spelled out here: see the note there
       const int64_t bytesA = (int64_t)(g.K / 32 - 1) * g.lda * 64 + (g.M - tm0) * 64, bytesW = (int64_t)(g.K / 32 - 1) * g.ldw * 64 + ((int64_t)g.N - tn0) * 64;
-      bd.ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(g.A)) + offA, 0, (int)bytesA, 0x00020000);
-      bd.rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(g.W)) + offW, 0, (int)bytesW, 0x00020000);
+      bd.ra = mh_buf_rsrc(reinterpret_cast<const char*>(g.A) + offA, (int)bytesA);
+      bd.rw = mh_buf_rsrc(reinterpret_cast<const char*>(g.W) + offW, (int)bytesW);
       return;
     }
     const int rl = lane >> 2, pc = lane & 3;
-    const int lc = pc ^ GSW[(rl >> 2) & 3];          // logical chunk stored at this physical slot
+    const int lc = pc ^ MH_GSW[(rl >> 2) & 3];          // logical chunk stored at this physical slot
 #pragma unroll
     for (int j = 0; j < C::PA; ++j) {
       int64_t ra = tm0 + ((wave * C::PA + j) % C::APIECES) * 16 + rl; if (ra >= g.M) ra = g.M - 1;
@@ -376,7 +368,7 @@ __global__ __launch_bounds__(C::THREADS, C::STAGE * C::NST <= 80 * 1024 ? 2 : 1)
     if (vn < g.ntiles) {
       set_sources(vn);
       if constexpr (!C::PP) {   // (the ping-pong loop ends on a barrier that every fragment read precedes)
-        __builtin_amdgcn_s_waitcnt(0xC07F);
+        mh_wait_lgkmcnt0();
         __builtin_amdgcn_s_barrier();
       }
       const int npro = nk < C::PRO ? nk : C::PRO;
@@ -408,22 +400,22 @@ __global__ __launch_bounds__(C::THREADS, C::STAGE * C::NST <= 80 * 1024 ? 2 : 1)
           lds_r[t] = float2{mean, 1.0f / sqrtf(var + g.d.eps)};
         }
       }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      mh_wait_lgkmcnt0_fence();
       __builtin_amdgcn_s_barrier();
     }
   };
   for (int vt = blockIdx.x; vt < g.ntiles; vt += gridDim.x) {
   if (!pre) {
     if (vt != (int)blockIdx.x) {   // the ring is reused: every wave must be done reading the previous tile's last stage
-      __builtin_amdgcn_s_waitcnt(0xC07F);
+      mh_wait_lgkmcnt0();
       __builtin_amdgcn_s_barrier();
     }
     set_sources(vt);
   }
-  const int bid = xcd_remap(vt, g.ntiles);
+  const int bid = mh_xcd_remap(vt, g.ntiles);
   const int64_t m0 = (int64_t)(bid / tiles_n) * C::BM;
   const int n0 = (bid % tiles_n) * C::BN;
-  const int frag_off = fr * 64 + ((fg ^ GSW[(fr >> 2) & 3]) << 4);
+  const int frag_off = fr * 64 + ((fg ^ MH_GSW[(fr >> 2) & 3]) << 4);
   const int a_off = wm * (TI * 16 * 64) + frag_off;
   const int wcol0 = n0 + wn * (TJ * 16);
   const int64_t wrow0 = m0 + wm * (TI * 16);
@@ -434,7 +426,7 @@ __global__ __launch_bounds__(C::THREADS, C::STAGE * C::NST <= 80 * 1024 ? 2 : 1)
   for (int j = 0; j < TJ; ++j) {
     const int jj = j & 3;
     const int row = (j >> 2) * 64 + (v_wave ? 16 * jj + fr : 32 * (jj >> 1) + 8 * (fr >> 2) + 4 * (jj & 1) + (fr & 3));
-    b_offs[j] = wn * (TJ * 16 * 64) + row * 64 + ((fg ^ GSW[(row >> 2) & 3]) << 4);
+    b_offs[j] = wn * (TJ * 16 * 64) + row * 64 + ((fg ^ MH_GSW[(row >> 2) & 3]) << 4);
   }
 
   f32x4 acc[TI][TJ];
@@ -599,7 +591,7 @@ __global__ __launch_bounds__(C::THREADS, C::STAGE * C::NST <= 80 * 1024 ? 2 : 1)
         // (Loading them group by group into registers cost four dependent round trips: there are no registers for more at once.)
         char* rbase = smem + ((wave + 1) * RES_W <= RING ? wave * RES_W : RING + C::BM * C::WN * 4 + 3 * C::BN * 4);
         if constexpr (!C::PP) {   // (the ping-pong loop ends on a barrier that every fragment read precedes; the plain loop does not)
-          __builtin_amdgcn_s_waitcnt(0xC07F);
+          mh_wait_lgkmcnt0();
           __builtin_amdgcn_s_barrier();
         }
 #pragma unroll
@@ -609,8 +601,7 @@ __global__ __launch_bounds__(C::THREADS, C::STAGE * C::NST <= 80 * 1024 ? 2 : 1)
           for (int i = 0; i < TI; ++i) {
             int64_t row = wrow0 + 16 * i + fr; if (!FULL && row >= g.M) row = g.M - 1;
             const int64_t ro = g.r_panel ? ((int64_t)(col >> 5) * g.ldr + row) * 32 + (col & 31) : row * g.ldr + col;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(res + ro),
-                                             (__attribute__((address_space(3))) void*)(rbase + (qh * TI + i) * 1024), 16, 0, MH_EPI3_RES_NT ? 2 : 0);
+            mh_glds16<MH_EPI3_RES_NT ? 2 : 0>(res + ro, rbase + (qh * TI + i) * 1024);
           }
         }
 #pragma unroll
@@ -639,7 +630,7 @@ __global__ __launch_bounds__(C::THREADS, C::STAGE * C::NST <= 80 * 1024 ? 2 : 1)
             }
           }
         }
-        wait_vmcnt<0>();
+        mh_wait_vmcnt<0>();
         float rs[TI];
 #pragma unroll
         for (int i = 0; i < TI; ++i) rs[i] = 0.f;
@@ -680,7 +671,7 @@ __global__ __launch_bounds__(C::THREADS, C::STAGE * C::NST <= 80 * 1024 ? 2 : 1)
             v += __shfl_xor(v, 32, 64);
             if (fg == 0) red[(wm * (TI * 16) + 16 * i + fr) * C::WN + wn] = v;
           }
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          mh_wait_lgkmcnt0_fence();
           __builtin_amdgcn_s_barrier();
 #pragma unroll
           for (int i = 0; i < TI; ++i) {
@@ -751,7 +742,7 @@ __global__ __launch_bounds__(C::THREADS, C::STAGE * C::NST <= 80 * 1024 ? 2 : 1)
         const char* rstage = smem + wave * (TI * (TJ / 2) * 1024);
         const char* gbstage = smem + C::NW * (TI * (TJ / 2) * 1024) + wave * 1024;
         if constexpr (RSTAGE) {
-          __builtin_amdgcn_s_waitcnt(0xC07F);      // (the plain main loop does not end on a barrier: every wave's fragment reads first)
+          mh_wait_lgkmcnt0();      // (the plain main loop does not end on a barrier: every wave's fragment reads first)
           __builtin_amdgcn_s_barrier();
 #pragma unroll
           for (int qh = 0; qh < TJ / 2; ++qh) {
@@ -761,8 +752,7 @@ __global__ __launch_bounds__(C::THREADS, C::STAGE * C::NST <= 80 * 1024 ? 2 : 1)
 #pragma unroll
             for (int i = 0; i < TI; ++i) {
               int64_t row = wrow0 + 16 * i + fr; if (!FULL && row >= g.M) row = g.M - 1;
-              __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(res + r_col + row * r_rs),
-                                               (__attribute__((address_space(3))) void*)const_cast<char*>(rstage + (qh * TI + i) * 1024), 16, 0, 0);
+              mh_glds16(res + r_col + row * r_rs, const_cast<char*>(rstage + (qh * TI + i) * 1024));
             }
           }
           // ... and the wave's 64 residual gains | shifts ride along as one more piece (lanes 0 - 15 gamma, 16 - 31 beta, the rest repeat):
@@ -771,10 +761,9 @@ __global__ __launch_bounds__(C::THREADS, C::STAGE * C::NST <= 80 * 1024 ? 2 : 1)
           {
             const int l32 = lane & 31, gc = wcol0 + 4 * (l32 & 15);
             const float* gsrc = (l32 < 16 ? g.d.r_gamma : g.d.r_beta) + ((FULL || gc + 4 <= g.N) ? gc : 0);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                             (__attribute__((address_space(3))) void*)const_cast<char*>(gbstage), 16, 0, 0);
+            mh_glds16(gsrc, const_cast<char*>(gbstage));
           }
-          wait_vmcnt<0>();     // (the bias loads above included: nothing the epilogue loads is pending behind its first store)
+          mh_wait_vmcnt<0>();     // (the bias loads above included: nothing the epilogue loads is pending behind its first store)
         }
 #pragma unroll
         for (int qh = 0; qh < TJ / 2; ++qh) {
@@ -896,7 +885,7 @@ __global__ __launch_bounds__(C::THREADS, C::STAGE * C::NST <= 80 * 1024 ? 2 : 1)
               b += __shfl_xor(b, 16, 64); b += __shfl_xor(b, 32, 64);
               if (fg == 0) lds_o[(wm * (TI * 16) + 16 * i + fr) * C::WN + wn] = float2{a, b};
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            mh_wait_lgkmcnt0_fence();
             __builtin_amdgcn_s_barrier();
             for (int t = tid; t < C::BM; t += C::THREADS) {
               float a = 0.f, b = 0.f;
@@ -921,7 +910,7 @@ int launch_big(const GemmArgs& g0, hipStream_t s, int batch) {
   const int64_t t2 = (int64_t)ceil_div(g.M, C::BM) * ceil_div(g.N, C::BN);
   MH_CHECK_ARG(t2 > 0 && t2 < (1ll << 31), "gemm: bad grid (M=%lld N=%d)", (long long)g.M, g.N);
   // persistent: one block per CU slot walks the tiles (no re-launch, the ring stays allocated)
-  const int cus = device_cus();
+  const int cus = mh_device_cus();
   const int per_cu = (C::STAGE * C::NST <= 80 * 1024 && C::NW <= 4) ? 2 : 1;
   const int64_t slots = (int64_t)cus * per_cu;
   g.ntiles = (int)t2;
@@ -933,7 +922,7 @@ int launch_big(const GemmArgs& g0, hipStream_t s, int batch) {
 #ifdef MH_ABLATE
                        !(g.dbg & 31) &&
 #endif
-                       (int64_t)(g.K / 32) * g.lda * 64 < (1ll << 31) && (int64_t)(g.K / 32) * g.ldw * 64 < (1ll << 31);
+                       mh_panel_desc_fits(g.K / 32, g.lda) && mh_panel_desc_fits(g.K / 32, g.ldw);
 #define MH_LAUNCH_BIG(EPI_, ACT_, BITS_)                                                                             \
   do {                                                                                                                \
     if (buf_dma) MH_LAUNCH((gemm_big_kernel<C, EPI_, ACT_, (BITS_) | 16384>), grid, block, 0, s, g);                  \

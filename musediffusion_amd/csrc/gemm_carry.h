@@ -29,7 +29,6 @@ __global__ __launch_bounds__(256, (VAR & 4) ? 2 : 1) void gemm_carry_kernel(cons
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  constexpr int GSW[4] = {0, 2, 3, 1};
   // block -> (column strip, run of m-tiles): the 32 blocks of an XCD (blockIdx % 8) cover a band of m-tiles x every column strip
   const int xcd = blockIdx.x & 7, jb = blockIdx.x >> 3;
   const int groups = ((int)gridDim.x >> 3) / tiles_n;
@@ -40,29 +39,27 @@ __global__ __launch_bounds__(256, (VAR & 4) ? 2 : 1) void gemm_carry_kernel(cons
   // stage DMA (gemm_big_kernel's BufDma form)
   int va, vw;
   {
-    const int rl = lane >> 2, lc = (lane & 3) ^ GSW[(rl >> 2) & 3];
+    const int rl = lane >> 2, lc = (lane & 3) ^ MH_GSW[(rl >> 2) & 3];
     va = ((wave * C::PA) * 16 + rl) * 64 + lc * 16;
     vw = ((wave * C::PW) * 16 + rl) * 64 + lc * 16;
   }
   const int ka = (int)(g.lda * 64), kw = (int)(g.ldw * 64);
   const int ldsA0 = wave * C::PA * 1024, ldsW0 = C::BM * 64 + wave * C::PW * 1024;
-  const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<char*>(reinterpret_cast<const char*>(g.W)) + (int64_t)n0 * 64, 0,
-      (int)((int64_t)(g.K / 32 - 1) * g.ldw * 64 + ((int64_t)g.N - n0) * 64), 0x00020000);
+  // (the bound is mh_panel_rsrc's, spelled out: see the note there)
+  const __amdgpu_buffer_rsrc_t rw = mh_buf_rsrc(reinterpret_cast<const char*>(g.W) + (int64_t)n0 * 64, (int)((int64_t)(g.K / 32 - 1) * g.ldw * 64 + ((int64_t)g.N - n0) * 64));
   auto a_rsrc = [&](int m_tile) {
     const int64_t tm0 = (int64_t)m_tile * C::BM;
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(g.A)) + tm0 * 64, 0,
-                                             (int)((int64_t)(g.K / 32 - 1) * g.lda * 64 + (g.M - tm0) * 64), 0x00020000);
+    return mh_buf_rsrc(reinterpret_cast<const char*>(g.A) + tm0 * 64, (int)((int64_t)(g.K / 32 - 1) * g.lda * 64 + (g.M - tm0) * 64));
   };
   auto issue = [&](const __amdgpu_buffer_rsrc_t& ra, int slot, int k) {
     char* base = smem + slot;
     static_for<0, C::PA>([&](auto jc) {
       constexpr int j = decltype(jc)::value;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (__attribute__((address_space(3))) void*)(base + ldsA0), 16, va, k * ka, j * 1024, 0);
+      mh_buf_lds16<j * 1024>(ra, base + ldsA0, va, k * ka);
     });
     static_for<0, C::PW>([&](auto jc) {
       constexpr int j = decltype(jc)::value;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (__attribute__((address_space(3))) void*)(base + ldsW0), 16, vw, k * kw, j * 1024, 0);
+      mh_buf_lds16<j * 1024>(rw, base + ldsW0, vw, k * kw);
     });
   };
 
@@ -77,8 +74,8 @@ __global__ __launch_bounds__(256, (VAR & 4) ? 2 : 1) void gemm_carry_kernel(cons
   int swa[2], swb[2];
 #pragma unroll
   for (int kk = 0; kk < 2; ++kk) {
-    swa[kk] = ((2 * kk + h) ^ GSW[(l31 >> 2) & 3]) << 4;
-    swb[kk] = ((2 * kk + h) ^ GSW[(wc >> 2) & 3]) << 4;
+    swa[kk] = ((2 * kk + h) ^ MH_GSW[(l31 >> 2) & 3]) << 4;
+    swb[kk] = ((2 * kk + h) ^ MH_GSW[(wc >> 2) & 3]) << 4;
   }
   bf16x8 fa[2][2][4], fb[2][2][2];
   auto load = [&](auto bufc, int slot) {
@@ -171,8 +168,8 @@ __global__ __launch_bounds__(256, (VAR & 4) ? 2 : 1) void gemm_carry_kernel(cons
     // (SEQ: a tile's 16 stores leave between its last K-step and the next tile's first: younger than the stages issued before them)
     constexpr int nst = NOEPI ? 0 : SEQ ? ((MODE != 0 && kt + 1 < NST) ? 16 : 0) : ((MODE != 0 && kt >= NST - 1) ? NST - 1 : 0);
     if constexpr (need_next) {
-      wait_vmcnt<young * C::PIECES + nst>();
-      __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): this wave's reads of stage kt (issued a K-step ago) are done: its slot may be refilled
+      mh_wait_vmcnt<young * C::PIECES + nst>();
+      mh_wait_lgkmcnt0();   // lgkmcnt(0): this wave's reads of stage kt (issued a K-step ago) are done: its slot may be refilled
       __builtin_amdgcn_s_barrier();
       if constexpr (dman) {
         if constexpr (kt + NST < NK) issue(ra_cur, so[kt % NST], kt + NST);
@@ -227,7 +224,7 @@ __global__ __launch_bounds__(256, (VAR & 4) ? 2 : 1) void gemm_carry_kernel(cons
 
   f32x16 accA[4][2], accB[4][2];
   static_for<0, NST>([&](auto kc) { issue(ra_cur, so[decltype(kc)::value], decltype(kc)::value); });
-  wait_vmcnt<(NST - 1) * C::PIECES>();     // stage 0 landed
+  mh_wait_vmcnt<(NST - 1) * C::PIECES>();     // stage 0 landed
   __builtin_amdgcn_s_barrier();
   load(std::integral_constant<int, 0>{}, so[0]);
   int t = 1;
@@ -272,10 +269,10 @@ int launch_carry(const GemmArgs& g0, int variant, hipStream_t s) {
   MH_CHECK_ARG(g.K == 512, "gemm_ffn1_carry: K = %d (the unrolled K loop is built for 512)", g.K);
   MH_CHECK_ARG(g.M % C::BM == 0 && g.N % C::BN == 0, "gemm_ffn1_carry: full tiles only (M %% 256, N %% 128)");
   MH_CHECK_ARG(g.a_panel && g.w_panel && g.o_panel && g.bias && !g.residual && !g.out_f32, "gemm_ffn1_carry: panel operands, panel bf16 output, bias");
-  MH_CHECK_ARG((int64_t)(g.K / 32) * g.lda * 64 < (1ll << 31) && (int64_t)(g.K / 32) * g.ldw * 64 < (1ll << 31), "gemm_ffn1_carry: operand too large for a 32-bit descriptor");
+  MH_CHECK_ARG(mh_panel_desc_fits(g.K / 32, g.lda) && mh_panel_desc_fits(g.K / 32, g.ldw), "gemm_ffn1_carry: operand too large for a 32-bit descriptor");
   const int tiles_m = (int)(g.M / C::BM), tiles_n = g.N / C::BN;
   // the largest grid of (8 XCDs) x (column strips) x (groups of m-tile runs) that fits the chip with an even run of >= 2 tiles per block
-  const int cus = device_cus();
+  const int cus = mh_device_cus();
   MH_CHECK_ARG(tiles_m % 8 == 0, "gemm_ffn1_carry: M / 256 must be a multiple of 8");
   const int mx = tiles_m / 8;
   int groups = 0;

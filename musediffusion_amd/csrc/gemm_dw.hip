@@ -52,8 +52,8 @@ __global__ __launch_bounds__(128 * WN, WN == 2 ? 2 : 1) void gemm_tn_kernel(cons
   // XCD-aware block mapping (round 6): the blocks of ONE token slice share its operand panels (every m-tile's A panels are read by all
   // n-tiles and vice versa), and workgroups go to the 8 XCDs round-robin - dealt out as (tile, slice) = (blockIdx.x, blockIdx.y) the 16 tiles
   // of a slice landed on all 8 L2s and every panel was fetched from HBM up to 8 times (rocprofv3 FETCH_SIZE: 313 MB per launch against
-  // 167 MB of operands).  xcd_remap gives each XCD a contiguous run of (slice, tile) pairs, i.e. whole slices.
-  const int vb = xcd_remap((int)blockIdx.x, (int)gridDim.x);
+  // 167 MB of operands).  mh_xcd_remap gives each XCD a contiguous run of (slice, tile) pairs, i.e. whole slices.
+  const int vb = mh_xcd_remap((int)blockIdx.x, (int)gridDim.x);
   const int slice_i = vb / g.tiles, tile_i = vb % g.tiles;
   const int m0 = (tile_i / tiles_n) * BMt, n0 = (tile_i % tiles_n) * BNt;
   // (uneven slices: the split count is chosen to fill the chip - 21 slices of a 12-tile output on 256 CUs - not to divide the K steps)
@@ -103,12 +103,10 @@ __global__ __launch_bounds__(128 * WN, WN == 2 ? 2 : 1) void gemm_tn_kernel(cons
     char* base = smem + (kt % NSTt) * STAGEt;
 #pragma unroll
     for (int j = 0; j < PAt; ++j)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcA[j] + (int64_t)kt * kadvA),
-                                       (__attribute__((address_space(3))) void*)(base + (wave * PAt + j) * 1024), 16, 0, 0);
+      mh_glds16(srcA[j] + (int64_t)kt * kadvA, base + (wave * PAt + j) * 1024);
 #pragma unroll
     for (int j = 0; j < PBt; ++j)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcB[j] + (int64_t)kt * kadvB),
-                                       (__attribute__((address_space(3))) void*)(base + ASTAGE + (wave * PBt + j) * 1024), 16, 0, 0);
+      mh_glds16(srcB[j] + (int64_t)kt * kadvB, base + ASTAGE + (wave * PBt + j) * 1024);
   };
   // transposing reads: lane 4q + p of a 16-lane group addresses row q, columns 4p .. 4p+3 of a (4 k) x (16 columns) block and
   // receives column (lane & 15) of the 4 rows.  Group = k-group fg: rows 8 fg + 4 half + q.
@@ -172,7 +170,7 @@ __global__ __launch_bounds__(128 * WN, WN == 2 ? 2 : 1) void gemm_tn_kernel(cons
   for (int st = 0; st < npro; ++st) issue(st);
   for (int kt = 0; kt < nk; ++kt) {
     const int younger = nk - 1 - kt < NSTt - 2 ? nk - 1 - kt : NSTt - 2;
-    wait_stages<PAt + PBt>(younger);
+    mh_wait_stages<PAt + PBt>(younger);
     __builtin_amdgcn_s_barrier();
     if (kt + NSTt - 1 < nk) issue(kt + NSTt - 1);
     const unsigned stage = (unsigned)((kt % NSTt) * STAGEt);
@@ -206,7 +204,7 @@ __global__ __launch_bounds__(128 * WN, WN == 2 ? 2 : 1) void gemm_tn_kernel(cons
         }
       }
     }
-    __builtin_amdgcn_s_waitcnt(0xC07F);
+    mh_wait_lgkmcnt0();
   }
   // D' tile (rows n, cols m): lane holds m = fr, n = 4 fg + r -> 4 consecutive n of one m: one 16-byte store
   float* outp = g.out + (int64_t)slice_i * g.slice;

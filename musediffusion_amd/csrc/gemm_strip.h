@@ -32,7 +32,6 @@ __global__ __launch_bounds__(256, 2) void gemm_strip_kernel(const GemmArgs g, in
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  constexpr int GSW[4] = {0, 2, 3, 1};
   // block -> a run of tiles.  The m-tiles are cut into nbands bands (8 = one per XCD: blockIdx % 8 under round-robin dispatch, so that an A
   // tile is fetched into ONE L2 and the W strips into all eight); a band's tiles are numbered strip-major (T = strip x band_m + m) and dealt
   // to the band's blocks in equal runs (they differ by at most one tile).  A run is at least two tiles and at most band_m: it walks down a
@@ -46,31 +45,30 @@ __global__ __launch_bounds__(256, 2) void gemm_strip_kernel(const GemmArgs g, in
   // stage DMA (gemm_big_kernel's BufDma form: tile base in a descriptor, K step as the scalar offset, a wave's pieces as immediates)
   int va, vw;
   {
-    const int rl = lane >> 2, lc = (lane & 3) ^ GSW[(rl >> 2) & 3];
+    const int rl = lane >> 2, lc = (lane & 3) ^ MH_GSW[(rl >> 2) & 3];
     va = ((wave * C::PA) * 16 + rl) * 64 + lc * 16;
     vw = ((wave * C::PW) * 16 + rl) * 64 + lc * 16;
   }
   const int ka = (int)(g.lda * 64), kw = (int)(g.ldw * 64);
   const int ldsA0 = wave * C::PA * 1024, ldsW0 = C::BM * 64 + wave * C::PW * 1024;
+  // (the bound is mh_panel_rsrc's, spelled out: see the note there)
   auto w_rsrc = [&](int strip) __attribute__((always_inline)) {
     const int64_t tn0 = (int64_t)strip * C::BN;
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(g.W)) + tn0 * 64, 0,
-                                             (int)((int64_t)(g.K / 32 - 1) * g.ldw * 64 + ((int64_t)g.N - tn0) * 64), 0x00020000);
+    return mh_buf_rsrc(reinterpret_cast<const char*>(g.W) + tn0 * 64, (int)((int64_t)(g.K / 32 - 1) * g.ldw * 64 + ((int64_t)g.N - tn0) * 64));
   };
   auto a_rsrc = [&](int m_tile) __attribute__((always_inline)) {
     const int64_t tm0 = (int64_t)m_tile * C::BM;
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(g.A)) + tm0 * 64, 0,
-                                             (int)((int64_t)(g.K / 32 - 1) * g.lda * 64 + (g.M - tm0) * 64), 0x00020000);
+    return mh_buf_rsrc(reinterpret_cast<const char*>(g.A) + tm0 * 64, (int)((int64_t)(g.K / 32 - 1) * g.lda * 64 + (g.M - tm0) * 64));
   };
   auto issue = [&](const __amdgpu_buffer_rsrc_t& ra, const __amdgpu_buffer_rsrc_t& rw, int slot, int k) __attribute__((always_inline)) {
     char* base = smem + slot;
     static_for<0, C::PA>([&](auto jc) {
       constexpr int j = decltype(jc)::value;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (__attribute__((address_space(3))) void*)(base + ldsA0), 16, va, k * ka, j * 1024, 0);
+      mh_buf_lds16<j * 1024>(ra, base + ldsA0, va, k * ka);
     });
     static_for<0, C::PW>([&](auto jc) {
       constexpr int j = decltype(jc)::value;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (__attribute__((address_space(3))) void*)(base + ldsW0), 16, vw, k * kw, j * 1024, 0);
+      mh_buf_lds16<j * 1024>(rw, base + ldsW0, vw, k * kw);
     });
   };
 
@@ -82,8 +80,8 @@ __global__ __launch_bounds__(256, 2) void gemm_strip_kernel(const GemmArgs g, in
   int swa[2], swb[2];
 #pragma unroll
   for (int kk = 0; kk < 2; ++kk) {
-    swa[kk] = ((2 * kk + h) ^ GSW[(l31 >> 2) & 3]) << 4;
-    swb[kk] = ((2 * kk + h) ^ GSW[(wc >> 2) & 3]) << 4;
+    swa[kk] = ((2 * kk + h) ^ MH_GSW[(l31 >> 2) & 3]) << 4;
+    swb[kk] = ((2 * kk + h) ^ MH_GSW[(wc >> 2) & 3]) << 4;
   }
   bf16x8 fa[2][2][4], fb[2][2][2];
   auto load = [&](auto bufc, int slot) __attribute__((always_inline)) {
@@ -179,8 +177,8 @@ __global__ __launch_bounds__(256, 2) void gemm_strip_kernel(const GemmArgs g, in
     // ... and, where stage kt + 1 was issued before the previous tile's epilogue, that tile's 16 stores
     constexpr int nst = (PREV && kt + 1 < NST) ? 16 : 0;
     if constexpr (need_next) {
-      wait_vmcnt<young * C::PIECES + nst>();
-      __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): this wave's reads of stage kt (issued a K-step ago) are done: its slot may be refilled
+      mh_wait_vmcnt<young * C::PIECES + nst>();
+      mh_wait_lgkmcnt0();   // lgkmcnt(0): this wave's reads of stage kt (issued a K-step ago) are done: its slot may be refilled
       __builtin_amdgcn_s_barrier();
       if constexpr (dman) {
         if constexpr (kt + NST < NK) issue(ra_cur, rw_cur, so[kt % NST], kt + NST);
@@ -229,7 +227,7 @@ __global__ __launch_bounds__(256, 2) void gemm_strip_kernel(const GemmArgs g, in
   };
 
   static_for<0, NST>([&](auto kc) { issue(ra_cur, rw_cur, so[decltype(kc)::value], decltype(kc)::value); });
-  wait_vmcnt<(NST - 1) * C::PIECES>();     // stage 0 landed
+  mh_wait_vmcnt<(NST - 1) * C::PIECES>();     // stage 0 landed
   __builtin_amdgcn_s_barrier();
   load(std::integral_constant<int, 0>{}, so[0]);
   using T = std::true_type;
@@ -248,7 +246,7 @@ bool strip_ok(const GemmArgs& g) {
   return g.a_panel && g.w_panel && g.o_panel && !g.out_f32 && !g.residual && !g.pre_out && !g.q && !g.ln_gamma && !g.drop.thr && !g.act_grad &&
          !g.d.a_stats && !g.d.r_stats && !g.d.o_stats && !(g.dbg & 127) && g.act == MH_ACT_GELU_ERF && g.bias && g.K == 512 &&
          g.M >= 2 * C::BM && g.M % C::BM == 0 && g.N % C::BN == 0 && g.sA == 0 && g.sW == 0 && g.sO == 0 &&
-         (int64_t)(g.K / 32) * g.lda * 64 < (1ll << 31) && (int64_t)(g.K / 32) * g.ldw * 64 < (1ll << 31);
+         mh_panel_desc_fits(g.K / 32, g.lda) && mh_panel_desc_fits(g.K / 32, g.ldw);
 }
 
 int launch_strip(const GemmArgs& g, hipStream_t s) {
@@ -256,7 +254,7 @@ int launch_strip(const GemmArgs& g, hipStream_t s) {
   const int tiles_m = (int)(g.M / C::BM), tiles_n = g.N / C::BN;
   // two blocks per CU.  Bands: one per XCD where the m-tiles divide by 8, else one; a band's blocks get equal runs of its tiles, a run
   // between 2 tiles (the kernel's first / last tile forms) and band_m (it crosses at most one strip boundary)
-  const int slots = 2 * device_cus();
+  const int slots = 2 * mh_device_cus();
   int nbands = (tiles_m % 8 == 0 && slots % 8 == 0) ? 8 : 1;
   int band_m = tiles_m / nbands;
   if (band_m < 2) { nbands = 1; band_m = tiles_m; }

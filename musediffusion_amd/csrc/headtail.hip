@@ -12,7 +12,7 @@
 // (conflict-free ds_read_b128 fragments); DMA pieces of 16 rows x 64 B with the swizzle on the SOURCE address; MFMA 16x16x32 bf16
 // issued as D = W_tile . A_tile^T with the W rows of a wave's 64 columns dealt to the MFMA input rows as
 // 32 (jj >> 1) + 8 (p >> 2) + 4 (jj & 1) + (p & 3), so that a lane owns 8 CONSECUTIVE output columns of one row.
-#include "common.h"
+#include "lds_dma.h"
 #include "step_update.h"
 
 namespace {
@@ -21,8 +21,9 @@ namespace {
 // network.py:44-46), where 64 rows of a 768-wide intermediate plus three weight stages would need 240 KB of LDS - there the ring has
 // TWO slots, refilled between a K step's fragment reads and its MFMAs (the same two stages in flight).  One K32 step of the A operand
 // = ROWS x 64 B (a "slab").
-// G = {0, 2, 3, 1} as a packed table (no memory lookup)
-__device__ __forceinline__ int ht_g(int x) { return (0x78 >> (2 * x)) & 3; }
+// MH_GSW (lds_dma.h) as a packed table (no memory lookup)
+__device__ __forceinline__ constexpr int ht_g(int x) { return (0x78 >> (2 * x)) & 3; }
+static_assert(ht_g(0) == MH_GSW[0] && ht_g(1) == MH_GSW[1] && ht_g(2) == MH_GSW[2] && ht_g(3) == MH_GSW[3], "ht_g is the chunk swizzle MH_GSW");
 
 struct HeadArgs {
   const float* x; int64_t rows; int E, E_pad, L;
@@ -54,8 +55,6 @@ struct TailArgs {
   StepRng rng; int has_rng;
 };
 
-template <int N> __device__ __forceinline__ void ht_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void ht_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 // one W stage (K32 step kt of a [K / 32][WROWS][32] panel matrix) into an LDS slot: WROWS / 16 pieces dealt over NW waves
 template <int WROWS, int NW>
@@ -66,8 +65,7 @@ __device__ __forceinline__ void ht_issue_w(const bf16* __restrict__ w, int kt, c
   for (int j = 0; j < PER; ++j) {
     const int p = (wave * PER + j) % PIECES;    // (fewer pieces than waves: the upper waves repeat a piece - same bytes, same address - so every wave's count is the same)
     const bf16* src = w + ((int64_t)kt * WROWS + p * 16 + rl) * 32 + lc * 8;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)(slot + p * 1024), 16, 0, 0);
+    mh_glds16(src, slot + p * 1024);
   }
 }
 
@@ -101,9 +99,9 @@ __device__ __forceinline__ void ht_loop(f32x4 (&acc)[RT][4], const bf16* __restr
   static_assert(NSLOT == 2 || NSLOT == 3, "ring of two or three slots");
   for (int st = issued; st < 2 && st < nk; ++st) ht_issue_w<WROWS, NW>(w, st, ring + (st % NSLOT) * slot_bytes, wave, lane);
   for (int kt = 0; kt < nk; ++kt) {
-    if (kt + 1 < nk) ht_wait_vmcnt<PER>(); else ht_wait_vmcnt<0>();    // this wave's stage kt has landed (stage kt + 1 may still fly)
+    if (kt + 1 < nk) mh_wait_vmcnt<PER>(); else mh_wait_vmcnt<0>();    // this wave's stage kt has landed (stage kt + 1 may still fly)
     if constexpr (NSLOT == 3) {
-      ht_lgkm0();                                                        // ... and its reads of stage kt - 1 are done: that slot is free
+      mh_wait_lgkmcnt0_fence();                                          // ... and its reads of stage kt - 1 are done: that slot is free
       if (kt + 2 < nk) ht_issue_w<WROWS, NW>(w, kt + 2, ring + ((kt + 2) % 3) * slot_bytes, wave, lane);
       ht_kstep<RT>(acc, a_base + kt * SLAB, ring + (kt % 3) * slot_bytes, a_off, b_offs);
     } else {
@@ -114,7 +112,7 @@ __device__ __forceinline__ void ht_loop(f32x4 (&acc)[RT][4], const bf16* __restr
       for (int j = 0; j < 4; ++j) b[j] = *reinterpret_cast<const bf16x8*>(w_slot + b_offs[j]);
 #pragma unroll
       for (int i = 0; i < RT; ++i) a[i] = *reinterpret_cast<const bf16x8*>(a_slab + a_off + i * 1024);
-      ht_lgkm0();                                                        // stage kt is in registers: its slot takes stage kt + 2
+      mh_wait_lgkmcnt0_fence();                                          // stage kt is in registers: its slot takes stage kt + 2
       if (kt + 2 < nk) ht_issue_w<WROWS, NW>(w, kt + 2, ring + (kt & 1) * slot_bytes, wave, lane);
 #pragma unroll
       for (int i = 0; i < RT; ++i)
@@ -167,10 +165,10 @@ __global__ __launch_bounds__(H / 64 * 64, H / 256) void head_fused_kernel(const 
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   // ---- phase 1: [64, E_pad] . W0^T
-  ht_lgkm0();
+  mh_wait_lgkmcnt0_fence();
   __builtin_amdgcn_s_barrier();           // the x tile is complete (the K loop itself has no barrier: its W stages are wave-private)
   ht_loop<H, NW, RT, NSLOT>(acc, g.w0, nk1, h1, ring, SLOT, a_off, b_offs, wave, lane, nk1 < 2 ? nk1 : 2);
-  ht_lgkm0();
+  mh_wait_lgkmcnt0_fence();
   __builtin_amdgcn_s_barrier();           // every wave is done with the x tile and the ring
   for (int st = 0; st < 2; ++st) ht_issue_w<H, NW>(g.w2, st, ring + (st % NSLOT) * SLOT, wave, lane);   // phase 2's first stages fly under the epilogue
   // epilogue 1: tanh(acc + b0) -> bf16 -> the A slabs of phase 2.  Lane: row 16 i + fr, columns 64 wave + 32 h + 8 fg + e
@@ -202,10 +200,10 @@ __global__ __launch_bounds__(H / 64 * 64, H / 256) void head_fused_kernel(const 
     for (int h = 0; h < 2; ++h) load8(prow + wave * 64 + 32 * h + 8 * fg, posv[h][i]);
   }
   // ---- phase 2: [64, H] . W2^T
-  ht_lgkm0();
+  mh_wait_lgkmcnt0_fence();
   __builtin_amdgcn_s_barrier();           // the tanh slabs are complete
   ht_loop<H, NW, RT, NSLOT>(acc, g.w2, NK2, h1, ring, SLOT, a_off, b_offs, wave, lane, 2);
-  ht_lgkm0();
+  mh_wait_lgkmcnt0_fence();
   __builtin_amdgcn_s_barrier();           // the ring is idle: its first bytes take the row statistics
   // ---- epilogue 2: (pos + (acc + b2)) + emb_t, LayerNorm over the row (two passes: in-lane -> 4 lanes -> NW waves through LDS)
   float* red = reinterpret_cast<float*>(ring);          // [64][NW]
@@ -247,7 +245,7 @@ __global__ __launch_bounds__(H / 64 * 64, H / 256) void head_fused_kernel(const 
       v += __shfl_xor(v, 32, 64);
       if (fg == 0) red[(16 * i + fr) * NW + wave] = v;
     }
-    ht_lgkm0();
+    mh_wait_lgkmcnt0_fence();
     __builtin_amdgcn_s_barrier();
 #pragma unroll
     for (int i = 0; i < RT; ++i) {
@@ -266,7 +264,7 @@ __global__ __launch_bounds__(H / 64 * 64, H / 256) void head_fused_kernel(const 
         rstd[i] = 1.0f / sqrtf(t * invH + g.eps);
       }
     }
-    ht_lgkm0();
+    mh_wait_lgkmcnt0_fence();
     __builtin_amdgcn_s_barrier();
   }
 #pragma unroll
@@ -318,8 +316,7 @@ __global__ __launch_bounds__(H / 64 * 64, H / 256) void tail_fused_kernel(const 
       const int p = wave * PER + j, kt = p / RT, rb = (p % RT) * 16;
       int64_t r = row0 + rb + rl; if (r >= g.rows) r = g.rows - 1;
       const bf16* src = g.X + ((int64_t)kt * g.ldx + r) * 32 + lc * 8;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                       (__attribute__((address_space(3))) void*)(h1 + kt * SLAB + rb * 64), 16, 0, 2);   // nt: read once
+      mh_glds16<2>(src, h1 + kt * SLAB + rb * 64);   // nt: read once
     }
   }
   for (int st = 0; st < 2; ++st) ht_issue_w<H, NW>(g.w0, st, ring + (st % NSLOT) * SLOT, wave, lane);
@@ -335,10 +332,10 @@ __global__ __launch_bounds__(H / 64 * 64, H / 256) void tail_fused_kernel(const 
   for (int i = 0; i < RT; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  ht_wait_vmcnt<2 * (H / 16 / NW)>();     // this wave's pieces of the A rows have landed (the two weight stages behind them may still fly)
+  mh_wait_vmcnt<2 * (H / 16 / NW)>();     // this wave's pieces of the A rows have landed (the two weight stages behind them may still fly)
   __builtin_amdgcn_s_barrier();           // ... and everybody else's: the A slabs are shared, the weight stages are wave-private
   ht_loop<H, NW, RT, NSLOT>(acc, g.w0, NK, h1, ring, SLOT, a_off, b_offs, wave, lane, 2);
-  ht_lgkm0();
+  mh_wait_lgkmcnt0_fence();
   __builtin_amdgcn_s_barrier();
   // second layer's weight stages: E rows x 64 B each
   const int E16 = g.E / 16;                       // 16-column groups of the output (8 for E = 128)
@@ -349,8 +346,7 @@ __global__ __launch_bounds__(H / 64 * 64, H / 256) void tail_fused_kernel(const 
     const int rl = lane >> 2, pc = lane & 3, lc = pc ^ ht_g((rl >> 2) & 3);
     const int p = wave % E16;
     const bf16* src = g.w2 + ((int64_t)kt * g.E + p * 16 + rl) * 32 + lc * 8;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)(ring + slot * SLOT + p * 1024), 16, 0, 0);
+    mh_glds16(src, ring + slot * SLOT + p * 1024);
   };
   if (w2_active) {
     issue2(0, 0);
@@ -375,14 +371,14 @@ __global__ __launch_bounds__(H / 64 * 64, H / 256) void tail_fused_kernel(const 
   f32x4 y[RT];
 #pragma unroll
   for (int i = 0; i < RT; ++i) y[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-  ht_lgkm0();
+  mh_wait_lgkmcnt0_fence();
   __builtin_amdgcn_s_barrier();                   // the tanh slabs are complete (the loop's weight pieces are wave-private: no barrier inside)
   if (w2_active)
   for (int kt = 0; kt < NK; ++kt) {
-    if (kt + 1 < NK) ht_wait_vmcnt<1>(); else ht_wait_vmcnt<0>();
+    if (kt + 1 < NK) mh_wait_vmcnt<1>(); else mh_wait_vmcnt<0>();
     bf16x8 b, a[RT];
     if constexpr (NSLOT == 3) {
-      ht_lgkm0();
+      mh_wait_lgkmcnt0_fence();
       if (kt + 2 < NK) issue2(kt + 2, (kt + 2) % 3);
       b = *reinterpret_cast<const bf16x8*>(ring + (kt % 3) * SLOT + b2_off);
 #pragma unroll
@@ -391,7 +387,7 @@ __global__ __launch_bounds__(H / 64 * 64, H / 256) void tail_fused_kernel(const 
       b = *reinterpret_cast<const bf16x8*>(ring + (kt & 1) * SLOT + b2_off);
 #pragma unroll
       for (int i = 0; i < RT; ++i) a[i] = *reinterpret_cast<const bf16x8*>(h1 + kt * SLAB + a_off + i * 1024);
-      ht_lgkm0();
+      mh_wait_lgkmcnt0_fence();
       if (kt + 2 < NK) issue2(kt + 2, kt & 1);
     }
 #pragma unroll
@@ -414,7 +410,7 @@ __global__ __launch_bounds__(H / 64 * 64, H / 256) void tail_fused_kernel(const 
   if constexpr (TJ3 > 0) {
     constexpr int VP = 16 * TJ3 * NW, SLOT3 = VP * 64, NK3 = 3 * 4;      // (E = 128: 4 slabs per part, 12 K32 steps)
     static_assert(2 * SLOT3 <= NSLOT * SLOT && NK3 * SLAB + (2 * ROWS * NW + ROWS) * 4 <= H1_BYTES, "rounding phase: LDS");
-    ht_lgkm0();
+    mh_wait_lgkmcnt0_fence();
     __builtin_amdgcn_s_barrier();           // every wave is past its last fragment read of phase 2: slabs and ring are free
     auto issue3 = [&](int kt) {
       const int rl = lane >> 2, pc = lane & 3, lc = pc ^ ht_g((rl >> 2) & 3);
@@ -422,8 +418,7 @@ __global__ __launch_bounds__(H / 64 * 64, H / 256) void tail_fused_kernel(const 
       for (int j = 0; j < TJ3; ++j) {
         const int p = wave * TJ3 + j;
         const bf16* src = g.tsplit + ((int64_t)kt * VP + p * 16 + rl) * 32 + lc * 8;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                         (__attribute__((address_space(3))) void*)(ring + (kt & 1) * SLOT3 + p * 1024), 16, 0, 0);
+        mh_glds16(src, ring + (kt & 1) * SLOT3 + p * 1024);
       }
     };
     issue3(0);
@@ -453,7 +448,7 @@ __global__ __launch_bounds__(H / 64 * 64, H / 256) void tail_fused_kernel(const 
         if (fg == 0) red[row * NW + wave] = v2;
       }
     }
-    ht_lgkm0();
+    mh_wait_lgkmcnt0_fence();
     __builtin_amdgcn_s_barrier();
     if (tid < ROWS) {
       float t = 0.f;
@@ -470,8 +465,8 @@ __global__ __launch_bounds__(H / 64 * 64, H / 256) void tail_fused_kernel(const 
 #pragma unroll
     for (int j = 0; j < TJ3; ++j) b3_offs[j] = ((wave * TJ3 + j) * 16 + fr) * 64 + ((fg ^ ht_g((fr >> 2) & 3)) << 4);
     for (int kt = 0; kt < NK3; ++kt) {            // (a wave's table rows are its own pieces: no barrier inside)
-      ht_wait_vmcnt<0>();                         // this wave's stage kt has landed
-      ht_lgkm0();                                 // ... and its reads of stage kt - 1 are done: that slot takes stage kt + 1
+      mh_wait_vmcnt<0>();                         // this wave's stage kt has landed
+      mh_wait_lgkmcnt0_fence();                   // ... and its reads of stage kt - 1 are done: that slot takes stage kt + 1
       if (kt + 1 < NK3) issue3(kt + 1);
       bf16x8 a[RT], b[TJ3];
 #pragma unroll
@@ -490,7 +485,7 @@ __global__ __launch_bounds__(H / 64 * 64, H / 256) void tail_fused_kernel(const 
       const f32x4 t4 = *reinterpret_cast<const f32x4*>(g.tnorm + (wave * TJ3 + j) * 16 + 4 * fg);
       tn[j][0] = t4[0]; tn[j][1] = t4[1]; tn[j][2] = t4[2]; tn[j][3] = t4[3];
     }
-    ht_lgkm0();
+    mh_wait_lgkmcnt0_fence();
     __builtin_amdgcn_s_barrier();               // (xn was written before the K loop's first barrier; `red` is reused below)
 #pragma unroll
     for (int i = 0; i < RT; ++i) {
@@ -515,7 +510,7 @@ __global__ __launch_bounds__(H / 64 * 64, H / 256) void tail_fused_kernel(const 
       }
       if (fg == 0) { red[(16 * i + fr) * NW + wave] = best; redi[(16 * i + fr) * NW + wave] = bi; }
     }
-    ht_lgkm0();
+    mh_wait_lgkmcnt0_fence();
     __builtin_amdgcn_s_barrier();
     if (tid < ROWS && row0 + tid < g.rows) {
       float best = -INFINITY;
@@ -531,7 +526,7 @@ __global__ __launch_bounds__(H / 64 * 64, H / 256) void tail_fused_kernel(const 
     }
     if (!g.x) return;
     // ---- the update of the block's rows: the arithmetic of step_epilogue4_kernel (step_update.h), 4 consecutive elements per thread
-    ht_lgkm0();
+    mh_wait_lgkmcnt0_fence();
     __builtin_amdgcn_s_barrier();
     const mh_step_coef c = *g.coef;
     uint32_t rng_step = 0;
@@ -566,7 +561,7 @@ __global__ __launch_bounds__(H / 64 * 64, H / 256) void tail_fused_kernel(const 
     return;
   }
   if (g.sqnorm) {   // |row|^2: 4 columns in the lane -> the 4 lanes of a row (xor 16, 32) -> the E / 16 waves through LDS, fixed order
-    ht_lgkm0();
+    mh_wait_lgkmcnt0_fence();
     __builtin_amdgcn_s_barrier();           // every wave is past its last fragment read: the ring's first bytes are free
     float* red = reinterpret_cast<float*>(ring);          // [64][NW]
 #pragma unroll
@@ -576,7 +571,7 @@ __global__ __launch_bounds__(H / 64 * 64, H / 256) void tail_fused_kernel(const 
       v += __shfl_xor(v, 32, 64);
       if (fg == 0) red[(16 * i + fr) * NW + wave] = v;
     }
-    ht_lgkm0();
+    mh_wait_lgkmcnt0_fence();
     __builtin_amdgcn_s_barrier();
     if (tid < ROWS) {
       float t = 0.f;

@@ -14,7 +14,7 @@
 // LayerNorm / residual sums / softmax statistics stay fp32; GELU is the exact erf form, tanh is tanhf (as in the fp32 mode).
 #include <type_traits>
 
-#include "common.h"
+#include "lds_dma.h"
 
 namespace {
 
@@ -210,17 +210,6 @@ struct SpGemmArgs {
 
 constexpr int GBM = 256, GBN = 128, GNST = 3, GSTAGE = (GBM + GBN) * 64, GTI = 8, GTJ = 4, GPA = 4, GPW = 2, GPIECES = GPA + GPW;
 
-template <int N> __device__ __forceinline__ void sp_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void sp_wait_stages(int stages) {
-  if (stages >= 2) sp_wait_vmcnt<2 * GPIECES>();
-  else if (stages == 1) sp_wait_vmcnt<GPIECES>();
-  else sp_wait_vmcnt<0>();
-}
-__device__ __forceinline__ int sp_xcd_remap(int bid, int nblk) {
-  const int q = nblk >> 3, r = nblk & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
-
 template <typename T, int ACT>
 __global__ __launch_bounds__(256, 2) void split_gemm_kernel(const SpGemmArgs g) {
   typedef typename Sp<T>::x8 x8;
@@ -231,21 +220,19 @@ __global__ __launch_bounds__(256, 2) void split_gemm_kernel(const SpGemmArgs g) 
   const int tiles_n = (g.N + GBN - 1) / GBN;
   const int nk0 = g.K / 32, nk = 2 * nk0;   // two DMA stages per K-step of 32 (three products: see `issue`)
   const int fr = lane & 15, fg = lane >> 4;
-  constexpr int GSW[4] = {0, 2, 3, 1};
   // DMA coordinates: a piece = 16 rows x 64 B; lane i lands at row i / 4, physical chunk i % 4, which holds logical chunk pc ^ G[..]
-  const int rl = lane >> 2, pc = lane & 3, lc = pc ^ GSW[(rl >> 2) & 3];
+  const int rl = lane >> 2, pc = lane & 3, lc = pc ^ MH_GSW[(rl >> 2) & 3];
   // The stage DMA as `buffer_load_dwordx4 ... lds` (round 5, as csrc/gemm_big.h BufDma): the tile's rows of part 0, panel 0 as the base of a buffer
   // descriptor (scalar registers), the (part, panel) of the stage as the instruction's scalar offset, a wave's consecutive pieces as its
   // immediate offset (which advances the LDS address with the buffer address) and ONE per-lane offset: no vector address arithmetic per piece.
-  // Rows beyond M / N are not clamped: inside the buffer they read other rows (never stored); the descriptor ends with the rows this operand OWNS in
-  // its last (part, panel) - A / W may be row windows of a larger buffer (the V^T projection: rows 2H.. of the stacked q | k | v weight) - so rows
-  // beyond them read as zeros instead of bytes behind the allocation.
+  // The two parts are 2 nk0 panels to the descriptor (mh_panel_rsrc); A / W may be row windows of a larger buffer (the V^T projection: rows 2H..
+  // of the stacked q | k | v weight).
   const int kbA = (int)(g.lda * 64), kbW = (int)(g.ldw * 64);
   const int va = ((wave * GPA) * 16 + rl) * 64 + lc * 16, vw = ((wave * GPW) * 16 + rl) * 64 + lc * 16;
   __amdgpu_buffer_rsrc_t rA, rW;
   auto set_sources = [&](int64_t m0, int n0) {
-    rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(g.A)) + m0 * 64, 0, (int)((2ll * nk0 - 1) * g.lda * 64 + (g.M - m0) * 64), 0x00020000);
-    rW = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(g.W)) + (int64_t)n0 * 64, 0, (int)((2ll * nk0 - 1) * g.ldw * 64 + ((int64_t)g.N - n0) * 64), 0x00020000);
+    rA = mh_panel_rsrc(g.A, m0, 2ll * nk0, g.lda, g.M);
+    rW = mh_panel_rsrc(g.W, (int64_t)n0, 2ll * nk0, g.ldw, (int64_t)g.N);
   };
   // Two DMA stages per K-step kk serve its three products: stage 2kk = {A lo, W hi}, stage 2kk+1 = {A hi, W lo}; the third product,
   // A hi x W hi, runs in the odd stage on the A fragments it holds and the W hi fragments KEPT IN REGISTERS from the even stage - no
@@ -254,30 +241,30 @@ __global__ __launch_bounds__(256, 2) void split_gemm_kernel(const SpGemmArgs g) 
     const int kk = kt >> 1, odd = kt & 1;
     const int offA = ((odd ? 0 : nk0) + kk) * kbA, offW = ((odd ? nk0 : 0) + kk) * kbW;
     char* base = smem + (kt % GNST) * GSTAGE;
-    auto la = (__attribute__((address_space(3))) void*)(base + (wave * GPA) * 1024);
-    auto lw = (__attribute__((address_space(3))) void*)(base + GBM * 64 + (wave * GPW) * 1024);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, la, 16, va, offA, 0, 0);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, la, 16, va, offA, 1024, 0);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, la, 16, va, offA, 2048, 0);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, la, 16, va, offA, 3072, 0);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rW, lw, 16, vw, offW, 0, 0);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rW, lw, 16, vw, offW, 1024, 0);
+    char* la = base + (wave * GPA) * 1024;
+    char* lw = base + GBM * 64 + (wave * GPW) * 1024;
+    mh_buf_lds16<0>(rA, la, va, offA);
+    mh_buf_lds16<1024>(rA, la, va, offA);
+    mh_buf_lds16<2048>(rA, la, va, offA);
+    mh_buf_lds16<3072>(rA, la, va, offA);
+    mh_buf_lds16<0>(rW, lw, vw, offW);
+    mh_buf_lds16<1024>(rW, lw, vw, offW);
     static_assert(GPA == 4 && GPW == 2, "piece counts are written out (immediate offsets must be literals)");
   };
-  const int frag_off = fr * 64 + ((fg ^ GSW[(fr >> 2) & 3]) << 4);
+  const int frag_off = fr * 64 + ((fg ^ MH_GSW[(fr >> 2) & 3]) << 4);
   const int a_off = wm * (GTI * 16 * 64) + frag_off;
   int b_offs[GTJ];
 #pragma unroll
   for (int j = 0; j < GTJ; ++j) {
     const int row = 32 * (j >> 1) + 8 * (fr >> 2) + 4 * (j & 1) + (fr & 3);
-    b_offs[j] = wn * (GTJ * 16 * 64) + row * 64 + ((fg ^ GSW[(row >> 2) & 3]) << 4);
+    b_offs[j] = wn * (GTJ * 16 * 64) + row * 64 + ((fg ^ MH_GSW[(row >> 2) & 3]) << 4);
   }
   // Persistent: gridDim.x blocks (two per CU) walk the g.ntiles output tiles; a tile's first stages are put in flight BEFORE the previous
   // tile's epilogue (the ring is idle then), so the pipeline fill of a 16-K-step tile hides behind the stores.
   const int npro = nk < GNST ? nk : GNST;
   bool pre = false;
   for (int tile = blockIdx.x; tile < g.ntiles; tile += gridDim.x) {
-  const int bid = sp_xcd_remap(tile, g.ntiles);
+  const int bid = mh_xcd_remap(tile, g.ntiles);
   const int64_t m0 = (int64_t)(bid / tiles_n) * GBM;
   const int n0 = (bid % tiles_n) * GBN;
   set_sources(m0, n0);   // (recomputed when prefetched: the pointers do not live across the epilogue)
@@ -287,10 +274,10 @@ __global__ __launch_bounds__(256, 2) void split_gemm_kernel(const SpGemmArgs g) 
 #pragma unroll
     for (int j = 0; j < GTJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   if (pre) {
-    sp_wait_vmcnt<0>();   // the prefetched stages and the previous epilogue's stores (one counter)
+    mh_wait_vmcnt<0>();   // the prefetched stages and the previous epilogue's stores (one counter)
   } else {
     for (int st = 0; st < npro; ++st) issue(st);
-    sp_wait_stages(npro - 1);
+    mh_wait_stages<GPIECES, 0, 2>(npro - 1);
   }
   __builtin_amdgcn_s_barrier();
   // W fragments by PART, not by stage: bA = W hi (the even stage's operand, used again by the odd stage's hi x hi product), bB = W lo (odd stages
@@ -309,8 +296,8 @@ __global__ __launch_bounds__(256, 2) void split_gemm_kernel(const SpGemmArgs g) 
     const char* Ws = As + GBM * 64;
     if constexpr (next) {
       const int younger = nk - 2 - kt < GNST - 2 ? nk - 2 - kt : GNST - 2;
-      sp_wait_stages(younger);
-      __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): this wave's reads of stage kt are done
+      mh_wait_stages<GPIECES, 0, 2>(younger);
+      mh_wait_lgkmcnt0();   // lgkmcnt(0): this wave's reads of stage kt are done
       __builtin_amdgcn_s_barrier();
       if (kt + GNST < nk) issue(kt + GNST);   // slot kt % NST: every wave has read stage kt out of it
       if constexpr (!ODD) {
@@ -348,8 +335,8 @@ __global__ __launch_bounds__(256, 2) void split_gemm_kernel(const SpGemmArgs g) 
   const int64_t wrow0 = m0 + wm * 128;
   pre = false;
   if (tile + (int)gridDim.x < g.ntiles) {
-    const int nb = sp_xcd_remap(tile + (int)gridDim.x, g.ntiles);
-    __builtin_amdgcn_s_waitcnt(0xC07F);
+    const int nb = mh_xcd_remap(tile + (int)gridDim.x, g.ntiles);
+    mh_wait_lgkmcnt0();
     __builtin_amdgcn_s_barrier();       // every wave has read the last stages out of the ring
     set_sources((int64_t)(nb / tiles_n) * GBM, (nb % tiles_n) * GBN);
     for (int st = 0; st < npro; ++st) issue(st);
@@ -416,11 +403,6 @@ __global__ __launch_bounds__(256, 2) void split_gemm_kernel(const SpGemmArgs g) 
 // full-row tile); stages per K-step: {A hi, W lo} then {A lo, W hi}, the hi x hi product on the A hi fragments kept from the first.
 // Epilogue as csrc/gemm_big.h EPI 3: two-pass statistics, in-lane -> the 4 lanes of a row -> the 4 column waves through LDS.
 constexpr int RBM = 128, RBN = 512, RNST = 3, RSTAGE = (RBM + RBN) * 64, RTI = 4, RTJ = 8, RPW = 4, RPIECES = 1 + RPW;
-__device__ __forceinline__ void sp_wait_stages_r(int stages) {
-  if (stages >= 2) sp_wait_vmcnt<2 * RPIECES>();
-  else if (stages == 1) sp_wait_vmcnt<RPIECES>();
-  else sp_wait_vmcnt<0>();
-}
 template <typename T>
 __global__ __launch_bounds__(512, 1) void split_gemm_ln_kernel(const SpGemmArgs g, const float* __restrict__ gamma, const float* __restrict__ beta, float eps) {
   typedef typename Sp<T>::x8 x8;
@@ -430,28 +412,26 @@ __global__ __launch_bounds__(512, 1) void split_gemm_ln_kernel(const SpGemmArgs 
   const int wm = wave >> 2, wn = wave & 3;
   const int nk0 = g.K / 32, nk = 2 * nk0;
   const int fr = lane & 15, fg = lane >> 4;
-  constexpr int GSW[4] = {0, 2, 3, 1};
   const int64_t m0 = (int64_t)blockIdx.x * RBM;
-  const int rl = lane >> 2, pc = lane & 3, lc = pc ^ GSW[(rl >> 2) & 3];
+  const int rl = lane >> 2, pc = lane & 3, lc = pc ^ MH_GSW[(rl >> 2) & 3];
   // (stage DMA as buffer loads: see split_gemm_kernel)
   const int kbA = (int)(g.lda * 64), kbW = (int)(g.ldw * 64);
   const int va = (wave * 16 + rl) * 64 + lc * 16, vw = ((wave * RPW) * 16 + rl) * 64 + lc * 16;
-  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(g.A)) + m0 * 64, 0,
-                                                                      (int)((2ll * nk0 - 1) * g.lda * 64 + (g.M - m0) * 64), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(g.W)), 0, (int)((2ll * nk0 - 1) * g.ldw * 64 + (int64_t)g.N * 64), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rA = mh_panel_rsrc(g.A, m0, 2ll * nk0, g.lda, g.M);
+  const __amdgpu_buffer_rsrc_t rW = mh_panel_rsrc(g.W, 0, 2ll * nk0, g.ldw, (int64_t)g.N);
   auto issue = [&](int kt) {
     const int kk = kt >> 1, odd = kt & 1;
     const int offA = ((odd ? nk0 : 0) + kk) * kbA, offW = ((odd ? 0 : nk0) + kk) * kbW;
     char* base = smem + (kt % RNST) * RSTAGE;
-    auto lw = (__attribute__((address_space(3))) void*)(base + RBM * 64 + (wave * RPW) * 1024);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, (__attribute__((address_space(3))) void*)(base + wave * 1024), 16, va, offA, 0, 0);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rW, lw, 16, vw, offW, 0, 0);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rW, lw, 16, vw, offW, 1024, 0);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rW, lw, 16, vw, offW, 2048, 0);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rW, lw, 16, vw, offW, 3072, 0);
+    char* lw = base + RBM * 64 + (wave * RPW) * 1024;
+    mh_buf_lds16<0>(rA, base + wave * 1024, va, offA);
+    mh_buf_lds16<0>(rW, lw, vw, offW);
+    mh_buf_lds16<1024>(rW, lw, vw, offW);
+    mh_buf_lds16<2048>(rW, lw, vw, offW);
+    mh_buf_lds16<3072>(rW, lw, vw, offW);
     static_assert(RPW == 4, "piece counts are written out (immediate offsets must be literals)");
   };
-  const int frag_off = fr * 64 + ((fg ^ GSW[(fr >> 2) & 3]) << 4);
+  const int frag_off = fr * 64 + ((fg ^ MH_GSW[(fr >> 2) & 3]) << 4);
   const int a_off = wm * (RTI * 16 * 64) + frag_off;
   // W fragment j reads row (j>>2) 64 + 32 ((j&3)>>1) + 8 (fr>>2) + 4 (j&1) + (fr&3) of the wave's 128: the lane's part of the address (and the
   // swizzle, which sees the row only through (2 (fr>>2) + (j&1)) & 3) takes two registers, the rest is a compile-time offset per j
@@ -459,7 +439,7 @@ __global__ __launch_bounds__(512, 1) void split_gemm_ln_kernel(const SpGemmArgs 
 #pragma unroll
   for (int p = 0; p < 2; ++p) {
     const int row = 8 * (fr >> 2) + 4 * p + (fr & 3);
-    b_base[p] = wn * (RTJ * 16 * 64) + row * 64 + ((fg ^ GSW[(row >> 2) & 3]) << 4);
+    b_base[p] = wn * (RTJ * 16 * 64) + row * 64 + ((fg ^ MH_GSW[(row >> 2) & 3]) << 4);
   }
   auto b_off = [&](int j) { return b_base[j & 1] + ((j >> 2) * 64 + 32 * ((j & 3) >> 1)) * 64; };
   f32x4 acc[RTI][RTJ];
@@ -469,7 +449,7 @@ __global__ __launch_bounds__(512, 1) void split_gemm_ln_kernel(const SpGemmArgs 
     for (int j = 0; j < RTJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int npro = nk < RNST ? nk : RNST;
   for (int st = 0; st < npro; ++st) issue(st);
-  sp_wait_stages_r(npro - 1);
+  mh_wait_stages<RPIECES, 0, 2>(npro - 1);
   __builtin_amdgcn_s_barrier();
   // (column-group-major MFMA order: a W fragment is re-read in place right after its last use, so only the four A fragments need a second
   // register set for the next stage - the tile's 128 accumulators leave no room for more at two waves per SIMD)
@@ -487,8 +467,8 @@ __global__ __launch_bounds__(512, 1) void split_gemm_ln_kernel(const SpGemmArgs 
     const char* Ws = As + RBM * 64;
     if constexpr (next) {
       const int younger = nk - 2 - kt < RNST - 2 ? nk - 2 - kt : RNST - 2;
-      sp_wait_stages_r(younger);
-      __builtin_amdgcn_s_waitcnt(0xC07F);
+      mh_wait_stages<RPIECES, 0, 2>(younger);
+      mh_wait_lgkmcnt0();
       __builtin_amdgcn_s_barrier();
       if (kt + RNST < nk) issue(kt + RNST);
       if constexpr (!ODD) {
@@ -559,7 +539,7 @@ __global__ __launch_bounds__(512, 1) void split_gemm_ln_kernel(const SpGemmArgs 
       v += __shfl_xor(v, 32, 64);
       if (fg == 0) red[(wm * 64 + 16 * i + fr) * 4 + wn] = v;
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    mh_wait_lgkmcnt0_fence();
     __builtin_amdgcn_s_barrier();
 #pragma unroll
     for (int i = 0; i < RTI; ++i) {
@@ -577,7 +557,7 @@ __global__ __launch_bounds__(512, 1) void split_gemm_ln_kernel(const SpGemmArgs 
         rstd[i] = 1.0f / sqrtf(t * invN + eps);
       }
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    mh_wait_lgkmcnt0_fence();
     __builtin_amdgcn_s_barrier();   // reads done before the second pass overwrites `red`
   }
   T* outT = reinterpret_cast<T*>(g.out);
@@ -603,7 +583,7 @@ __global__ __launch_bounds__(512, 1) void split_gemm_ln_kernel(const SpGemmArgs 
 
 template <typename T>
 int launch_gemm_ln(const SpGemmArgs& g, const float* gamma, const float* beta, float eps, hipStream_t s) {
-  MH_CHECK_ARG((int64_t)(g.K / 16) * g.lda * 64 < (1ll << 31) && (int64_t)(g.K / 16) * g.ldw * 64 < (1ll << 31),
+  MH_CHECK_ARG(mh_panel_desc_fits(g.K / 16, g.lda) && mh_panel_desc_fits(g.K / 16, g.ldw),   // (K / 16 panels: two parts)
                "split_gemm_res_ln: an operand beyond 2 GiB (K=%d lda=%lld ldw=%lld): buffer-descriptor addressing is 32-bit", g.K, (long long)g.lda, (long long)g.ldw);
   const dim3 grid((unsigned)((g.M + RBM - 1) / RBM)), block(512);
   mh_prof_note("split tile=128x512 +LN M=%lld N=%d K=3x%d dtype=%s", (long long)g.M, g.N, g.K, sp_name<T>());
@@ -612,25 +592,16 @@ int launch_gemm_ln(const SpGemmArgs& g, const float* gamma, const float* beta, f
   return MH_OK;
 }
 
-inline int sp_device_cus() {
-  static int cus[MH_MAX_DEVICES] = {0};
-  const int dev = mh_current_device();
-  if (!cus[dev]) {
-    int n = 0;
-    cus[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-  }
-  return cus[dev];
-}
 template <typename T>
 int launch_gemm(const SpGemmArgs& g0, int act, hipStream_t s) {
   const int64_t tiles = (int64_t)((g0.M + GBM - 1) / GBM) * ((g0.N + GBN - 1) / GBN);
   MH_CHECK_ARG(tiles > 0 && tiles < (1ll << 31), "split_gemm: bad grid (M=%lld N=%d)", (long long)g0.M, g0.N);
-  MH_CHECK_ARG((int64_t)(g0.K / 16) * g0.lda * 64 < (1ll << 31) && (int64_t)(g0.K / 16) * g0.ldw * 64 < (1ll << 31),
+  MH_CHECK_ARG(mh_panel_desc_fits(g0.K / 16, g0.lda) && mh_panel_desc_fits(g0.K / 16, g0.ldw),   // (K / 16 panels: two parts)
                "split_gemm: an operand of [2][K/32][ld][32] beyond 2 GiB (K=%d lda=%lld ldw=%lld): buffer-descriptor addressing is 32-bit", g0.K,
                (long long)g0.lda, (long long)g0.ldw);
   SpGemmArgs g = g0;
   g.ntiles = (int)tiles;
-  const int64_t slots = 2 * (int64_t)sp_device_cus();
+  const int64_t slots = 2 * (int64_t)mh_device_cus();
   const dim3 grid((unsigned)(tiles < slots ? tiles : slots)), block(256);
   mh_prof_note("split tile=256x128 act=%d M=%lld N=%d K=3x%d out=%d dtype=%s bias=%s res=%d nt=%d ntiles=%d", act, (long long)g.M, g.N, g.K, g.out_mode,
                sp_name<T>(), !g.bias ? "0" : (g.bias_rows ? "row" : "col"), g.res ? 1 : 0, g.stream_out, g.ntiles);

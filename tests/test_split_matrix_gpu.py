@@ -1,7 +1,7 @@
 """Parity matrix of the split-precision kernels (csrc/split.hip): every C entry point called through the library's ABI against a float64
 reference on the CPU (tests/split_ref.py), EVERY element of EVERY output, in both part types, at the smallest shapes at which each path
 of a kernel exists - K = 32 (two DMA stages: prologue and peeled stages only), K = 64 (the first in-loop issue inside the peeled even
-stage), K = 96; ragged M and N in every output form; a persistent launch whose tile count leaves sp_xcd_remap a remainder and whose
+stage), K = 96; ragged M and N in every output form; a persistent launch whose tile count leaves mh_xcd_remap a remainder and whose
 fast and guarded epilogues both run after a prefetch and without one; the non-temporal stores; operands that are row windows of larger
 buffers, the stacked q | k | v weight of the V^T projection exactly as csrc/engine.hip passes it; one key tile with 56 masked keys, a last
 key tile of 8 keys, the first 8-wave launch, the half-empty d tile of head dim 16; LayerNorm rows with four active lanes, a lane-dependent
