@@ -1,7 +1,7 @@
-"""The C ABI as ctypes, read from the headers that define it (include/musehip.h, include/musehip_dbg.h).
+"""The C ABI as ctypes, read from the headers that define it (include/musehip.h, include/musehip_dbg.h, include/musehip_data.h).
 
 `load(name)` gives the header's enumerators (name -> int), its structs (name -> ctypes.Structure class) and its prototypes
-(name -> (restype, argtypes)).  The reader knows the C these two headers are written in and nothing more: a declaration it does not
+(name -> (restype, argtypes)).  The reader knows the C these headers are written in and nothing more: a declaration it does not
 recognise raises AbiError naming it - nothing is guessed and nothing is skipped.  tests/test_abi_cpu.py checks the result against
 the compiler.
 """

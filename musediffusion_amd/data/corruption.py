@@ -8,6 +8,7 @@ per-token Python loop (the reference spends O(tokens) interpreter steps per sequ
 """
 import random as _random
 
+import numpy as np
 import torch
 
 from .._lib import check, current_stream, lib, ptr, require_device
@@ -94,7 +95,8 @@ class Corruptions:
     """Same configuration surface as the reference's class (corruption.py:11-57: `corr_available`, `corr_max`, `corr_p`,
     `corr_kwargs`); `__call__(values, offsets)` corrupts a whole ragged batch on the device.  As in the reference the
     available corruptions are shuffled, the first `corr_max` are kept and each is applied with probability `corr_p` -
-    decided once per call (per batch), where the reference decides per sequence."""
+    decided once per call (per batch) by default, and per sequence as the reference does with `per_sequence=True` (what
+    data.load_data_music uses)."""
 
     MAP = {"mt": (masking_token, {"p": 0.3}), "mn": (masking_note, {"p": 0.5}), "rn": (randomize_note, {"p": 0.5}),
            "rr": (random_rotating, {"count": 3})}
@@ -109,15 +111,62 @@ class Corruptions:
         assert corr_kwargs is None or isinstance(corr_kwargs, dict)
         self.corr_available, self.corr_max, self.corr_p, self.corr_kwargs = tuple(corr_available), corr_max, corr_p, corr_kwargs
 
-    def __call__(self, values, offsets):
+    def _kwargs(self, key):
+        fn, defaults = self.MAP[key]
+        return fn, {k: (self.corr_kwargs or {}).get(k, v) for k, v in defaults.items()}
+
+    def draw_choices(self, B):
+        """The reference's decision, once per row (corruption.py:51-55), from the module's host `generator`: shuffle the available
+        corruptions, keep the first corr_max, one random() per kept slot.  -> int32 [B, corr_max]: entry [b, r] is the index into
+        corr_available of the corruption that fires for row b in slot r, or -1.  (The reference interleaves the corruptions' own draws
+        with these on one stream; here those come from the device generator, so the host stream holds the decisions alone.)"""
+        out = np.full((B, self.corr_max), -1, np.int32)
+        for b in range(B):
+            order = list(range(len(self.corr_available)))
+            generator.shuffle(order)
+            for r in range(self.corr_max):
+                if generator.random() > 1 - self.corr_p:
+                    out[b, r] = order[r]
+        return out
+
+    def __call__(self, values, offsets, *, per_sequence=False, choices=None, draws=None):
+        """per_sequence=False: one decision for the whole batch (below).  per_sequence=True: the reference's per-row decision.
+        `choices` (host int32 [B, corr_max], default draw_choices(B)) says which corruption fires for which row in which slot.  Slot by
+        slot, every kind present in the slot is applied to the whole batch as it stood when the slot began, and a row select keeps each
+        row's own result - all four corruptions keep the row lengths, so the offsets are shared.  The number of launches depends on
+        the kinds present, not on B.  `draws`: optional {(slot, key): keyword arguments of that corruption function} - the draws the
+        reference made, laid out as the functions document them (rows that do not take the kind may hold anything)."""
+        if per_sequence:
+            return self._per_sequence(values, offsets, choices, draws or {})
+        assert choices is None and draws is None, "choices / draws belong to per_sequence=True"
         order = list(self.corr_available)
         generator.shuffle(order)
         out = values
         for key in order[: self.corr_max]:
             if generator.random() > 1 - self.corr_p:
-                fn, defaults = self.MAP[key]
-                kw = {k: (self.corr_kwargs or {}).get(k, v) for k, v in defaults.items()}
+                fn, kw = self._kwargs(key)
                 out = fn(out, offsets, **kw)
+        return out
+
+    def _per_sequence(self, values, offsets, choices, draws):
+        from .wrapper import select_rows
+        values, offsets, B = _prep(values, offsets)
+        choices = self.draw_choices(B) if choices is None else np.asarray(choices.cpu() if torch.is_tensor(choices) else choices, np.int32)
+        assert choices.shape == (B, self.corr_max), (choices.shape, B, self.corr_max)
+        assert ((choices >= -1) & (choices < len(self.corr_available))).all()
+        out = values
+        for r in range(self.corr_max):
+            cur, nxt = out, None                         # every kind of the slot reads `cur`; `values` itself is never written
+            for k, key in enumerate(self.corr_available):
+                take = choices[:, r] == k
+                if not take.any():
+                    continue
+                fn, kw = self._kwargs(key)
+                res = fn(cur, offsets, **kw, **draws.get((r, key), {}))
+                take = torch.from_numpy(take.astype(np.int32)).to(values.device)
+                nxt = select_rows(cur, res, offsets, take) if nxt is None else select_rows(nxt, res, offsets, take, out=nxt)
+            if nxt is not None:
+                out = nxt
         return out
 
     def __repr__(self):

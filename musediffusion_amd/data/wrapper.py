@@ -1,4 +1,5 @@
-"""collate_batches of MuseDiffusion/data/wrapper.py:90-127 on the device: ragged fields -> padded [B, seq_len] tensors."""
+"""collate_batches of MuseDiffusion/data/wrapper.py:90-127 on the device: ragged fields -> padded [B, seq_len] tensors; and the two
+ragged tools of the dataset loader (data/dataset.py): gather rows by index, select rows between two buffers."""
 import torch
 
 from .._lib import check, current_stream, lib, ptr, require_device
@@ -11,6 +12,42 @@ def to_ragged(rows, device):
     offsets[1:] = torch.cumsum(lens, 0)
     values = torch.cat([torch.as_tensor(r, dtype=torch.int32).reshape(-1) for r in rows]) if rows else torch.zeros(0, dtype=torch.int32)
     return values.to(device), offsets.to(device)
+
+
+def gather_rows(fields, src_offsets, idx, cap, return_status=False):
+    """rows idx[b] of a ragged source -> a ragged batch (csrc/loader.hip).  fields: dict name -> int32 values sharing `src_offsets`
+    (int64 [n + 1]); idx int64 [B] on the device; cap: tokens each output field has room for (B x the longest source row always
+    fits, and sizing it so needs no sync).  Returns ({name: values [cap]}, offsets int64 [B + 1], length int32 [B]) and, on request,
+    status [B]: 1 = index outside [0, n), 2 = the row did not fit cap; such rows are empty.  Two + len(fields) launches."""
+    require_device(src_offsets, idx)
+    dev = src_offsets.device
+    idx = idx.to(device=dev, dtype=torch.int64).contiguous()
+    src_offsets = src_offsets.to(torch.int64).contiguous()
+    B, n, cap = idx.numel(), src_offsets.numel() - 1, int(cap)
+    offsets = torch.empty(B + 1, device=dev, dtype=torch.int64)
+    length, status = torch.empty(B, device=dev, dtype=torch.int32), torch.empty(B, device=dev, dtype=torch.int32)
+    check(lib().mhd_gather_offsets(ptr(src_offsets), n, ptr(idx), ptr(offsets), ptr(length), ptr(status), B, cap, current_stream()),
+          "mhd_gather_offsets")
+    out = {}
+    for name, vals in fields.items():
+        require_device(vals)
+        vals = vals.to(torch.int32).contiguous()
+        out[name] = torch.empty(max(cap, 1), device=dev, dtype=torch.int32)
+        check(lib().mhd_gather_rows(ptr(vals), ptr(src_offsets), n, ptr(idx), ptr(offsets), ptr(length), ptr(out[name]), B, cap,
+                                    current_stream()), "mhd_gather_rows")
+    return (out, offsets, length, status) if return_status else (out, offsets, length)
+
+
+def select_rows(a_values, b_values, offsets, take_b, out=None):
+    """out row b = take_b[b] ? row b of b_values : row b of a_values, for ragged buffers sharing `offsets`; out may be a_values"""
+    require_device(a_values, b_values, offsets, take_b)
+    assert a_values.dtype == b_values.dtype == torch.int32 and a_values.is_contiguous() and b_values.is_contiguous()
+    take_b = take_b.to(torch.int32).contiguous()
+    offsets = offsets.to(torch.int64).contiguous()
+    out = torch.empty_like(a_values) if out is None else out
+    check(lib().mhd_select_rows(ptr(a_values), ptr(b_values), ptr(offsets), ptr(take_b), ptr(out), offsets.numel() - 1, current_stream()),
+          "mhd_select_rows")
+    return out
 
 
 def _pad(values, offsets, L, pad, want_length=False):
