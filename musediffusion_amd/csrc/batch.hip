@@ -95,8 +95,9 @@ __global__ void corrupt_note_kernel(const int32_t* __restrict__ values, const in
   for (int j = threadIdx.x; j < n; j += TB) {
     int32_t v = values[off + j];
     if constexpr (MODE == 0) {
-      // zeroed when a firing velocity token sits at idx in [j-2, j+1] (it clears idx-1 .. idx+2); idx = 0 clears seq[-1:3] = nothing
-      bool z = false;
+      // zeroed when a firing velocity token sits at idx in [j-2, j+1] (it clears idx-1 .. idx+2).  idx = 0 clears the reference's
+      // seq[-1:3]: nothing in a longer row, and seq[2:3] - the last token - in a row of exactly 3 tokens
+      bool z = n == 3 && j == 2 && rank_of[0] >= 0;
 #pragma unroll
       for (int d = -2; d <= 1; ++d) {
         const int idx = j + d;
@@ -113,11 +114,17 @@ __global__ void corrupt_note_kernel(const int32_t* __restrict__ values, const in
   }
 }
 
-// random_rotating (corruption.py:165-195): `count` bar swaps; bar starts and the last EOS come from the INPUT row once
+// random_rotating (corruption.py:165-195): `count` bar swaps; bar starts and the last EOS come from the INPUT row once.
+// `bars` holds one entry per token of the longest row (a row of nothing but BAR tokens has MAX_ROW of them), so every pair the range
+// check below lets through names a recorded bar: a row within MAX_ROW is rotated as the reference rotates it or flagged, never
+// permuted from a bar start that was not recorded.  Static LDS: 32 KiB buf + 16 KiB bars.
+// status[b]: 0 rotated; 1 flagged - fewer than 2 bars, no EOS, a pair that is unsorted or out of range, or a last EOS in front of the
+// second bar (the row is a permutation of its input: the swaps before the offending pair are applied, the rest are not);
+// 2 a row longer than MAX_ROW, copied through
 __global__ void corrupt_rr_kernel(const int32_t* __restrict__ values, const int64_t* __restrict__ offsets, const int32_t* __restrict__ pairs,
                                   int count, int32_t* __restrict__ out, int32_t* __restrict__ status) {
   __shared__ int32_t buf[2][MAX_ROW];
-  __shared__ int bars[MAX_ROW / 2];
+  __shared__ int bars[MAX_ROW];
   __shared__ int wsum[4];
   __shared__ int eos_s, nbar_s;
   const int b = blockIdx.x;
@@ -142,7 +149,7 @@ __global__ void corrupt_rr_kernel(const int32_t* __restrict__ values, const int6
     }
     int total;
     const int r = carry + block_excl_scan(isbar, wsum, total);
-    if (isbar && r < MAX_ROW / 2) bars[r] = j;
+    if (isbar && r < MAX_ROW) bars[r] = j;
     carry += total;
   }
   if (last_eos >= 0) atomicMax(&eos_s, last_eos);

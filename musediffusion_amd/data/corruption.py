@@ -3,8 +3,21 @@
 A batch is (`values`, `offsets`): every sequence back to back in one int32 device tensor plus int64 row starts
 ([B + 1]).  Each function takes its random draws as optional arguments; given the draws the reference made (in
 the order it made them) the result is bit-identical to the reference's (tests/test_batch_gpu.py against
-tests/golden/batch.npz).  Without them the draws come from torch's device generator - same distribution, and no
+tests/golden/batch.npz; tests/test_batch_matrix_gpu.py on the edge rows of tests/batch_cases.py, where the reference's
+own slicing decides - masking_note on a 3-token row whose velocity token sits at index 0 clears the last token, as the
+reference's seq[-1:3] does).  Without them the draws come from torch's device generator - same distribution, and no
 per-token Python loop (the reference spends O(tokens) interpreter steps per sequence, corruption.py:108-114, :128-133).
+
+Where this module differs from the reference, on purpose:
+  * rows are limited to mh_batch_max_row() = 4096 tokens (the row lives in LDS); masking_note, randomize_note and
+    random_rotating raise ValueError on a longer one.  Handed straight to the C ABI such a row is copied through.
+  * random_rotating never raises and never changes a row's length: it FLAGS.  status 0 = rotated exactly as the reference
+    rotates; 1 = fewer than two bars (the reference: AssertionError), no EOS (IndexError), a pair that is unsorted, equal
+    or out of range (the reference cannot draw one), or a last EOS in front of the second bar (the reference returns a
+    longer row with tokens duplicated) - the row is then a permutation of its input: the swaps before the offending pair
+    are applied, the rest are not; 2 = longer than the row limit, copied through.  A row with fewer than two bars is
+    flagged (and left unchanged) for count = 0 too, where the reference's assert, inside its loop, never runs.  The kernel's bar table has one entry per token of the
+    longest row, so a legal row of any number of bars (4096 BAR tokens at most) is rotated, not flagged.
 """
 import random as _random
 
@@ -78,7 +91,8 @@ def _draw_bar_pairs(values, offsets, count):
 
 
 def random_rotating(values, offsets, count=3, pairs=None, return_status=False):
-    """corruption.py:165-195.  pairs [B, count, 2]: the sorted bar indices of each swap."""
+    """corruption.py:165-195.  pairs [B, count, 2]: the sorted bar indices of each swap.  return_status: also int32 [B], 0 rotated as
+    the reference does / 1 flagged (a permutation of the input row) / 2 too long (unchanged) - see the module docstring."""
     values, offsets, B = _prep(values, offsets)
     _check_rows(offsets)
     pairs = _draw_bar_pairs(values, offsets, count) if pairs is None else pairs

@@ -63,7 +63,9 @@ def _pad(values, offsets, L, pad, want_length=False):
 def collate_batches(fields, offsets, seq_len=None):
     """fields: dict name -> ragged int32 values sharing `offsets` (keys as in the reference: 'input_ids', 'input_mask',
     optional 'correct_ids', 'label').  Returns the reference's dict: ids / correct_ids / label zero padded, input_mask
-    padded with ONES, plus 'length' (wrapper.py:100-127).  seq_len None = the longest row (one host sync to read it)."""
+    padded with ONES, plus 'length' (wrapper.py:100-127).  seq_len None = the longest row (one host sync to read it).
+    Unlike the reference, which raises on a row longer than seq_len, such a row is truncated to its first seq_len tokens and
+    'length' still reports its full length (so length[b] > seq_len marks it); an empty row is all padding with length 0."""
     L = int(seq_len) if seq_len else int((offsets[1:] - offsets[:-1]).max())
     out = {}
     for name, vals in fields.items():

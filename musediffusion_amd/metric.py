@@ -2,7 +2,16 @@
 
 The reference walks every sequence token by token in Python (`get_vectors`) and then multiplies three small similarity
 matrices; here one kernel launch extracts the [32 rhythm | 12 melody | 12 harmony] features of all sequences and the
-three similarity matrices come from the library's exact-fp32 MFMA GEMM."""
+three similarity matrices come from the library's exact-fp32 MFMA GEMM.
+
+Where this module differs from the reference, on purpose (pinned by tests/test_batch_matrix_gpu.py):
+  * get_vectors never raises: status 1 = no BAR token (the reference: IndexError), 2 = a malformed note group or a row that ends
+    without terminator (ValueError / IndexError); the vectors of a flagged row mean nothing.
+  * a row with no position token between its first BAR and its EOS ([2, 1]) makes the reference read an unassigned variable
+    (UnboundLocalError); here it gets status 0, flat rhythm and melody vectors and, like any row without notes (chords only), the
+    0 / 0 = NaN harmony vector the reference returns for those.
+  * Controllability_Pitch judges a range token (meta[3]) outside 630..637 by the nearest range (below 631 as 631, above 637 as
+    637) where the reference raises KeyError; a row without pitch tokens counts as wrong, as the reference's NaN mean does."""
 import torch
 
 from ._lib import check, current_stream, lib, ptr, require_device

@@ -133,10 +133,12 @@ def validate(tokens, length):
     return int(eos[0]), once, rigid
 
 
-def msim_vectors(midi, note_len=128):
+def msim_vectors(midi, note_len=128, ref_unbound=True):
     """metric.py:4-71 get_vectors: [32 rhythm | 12 melody | 12 harmony] fp32, each L2-normalised.  `midi` = note tokens from
     anywhere before the first BAR up to the EOS / padding.  The amplitude expression is evaluated in double and rounded to
-    fp32 on store, as Python floats assigned into a float32 tensor are."""
+    fp32 on store, as Python floats assigned into a float32 tensor are.  A row that ends before any position token (BAR then
+    EOS) makes the reference read its `startp` before assigning it: UnboundLocalError, raised here too unless ref_unbound=False,
+    which gives the vectors the device kernel is pinned to on such a row (flat rhythm and melody, 0 / 0 harmony)."""
     f32 = np.float32
     i = 0
     while midi[i] != BAR:
@@ -159,6 +161,8 @@ def msim_vectors(midi, note_len=128):
             if midi[i - 1] == BAR:
                 prev_startp = -1
                 continue
+            if startp is None and ref_unbound:
+                raise UnboundLocalError("startp")
             if prev_startp != startp and prev_hi >= 0:
                 melody[(cur_hi - prev_hi) % 12] += 1
             break
