@@ -96,3 +96,86 @@ def Controllability_Velocity(metas, tokens, lengths=None):
     c = _counts(metas, tokens, lengths)
     use = (metas[:, 8].long() - 524) != 130
     return int(c[use, 2].sum()), int(c[use, 3].sum())
+
+
+# ------------------------------------------------------------------------------------------ fused 1-NN (csrc/evaluate.hip), additions
+def _mask_i32(mask, n, device):
+    if mask is None:
+        return None
+    require_device(mask)
+    assert mask.shape == (n,), "a validity mask holds one entry per row"
+    return (mask != 0).to(device=device, dtype=torch.int32).contiguous()
+
+
+def nearest(vec, keys=None, valid=None, keys_valid=None, return_values=False, return_sim=False):
+    """For every row of vec [nq, 56] (get_vectors' layout) the index of its most similar row of keys [nk, 56] under the MSIM similarity
+    of metric.py:100-103, by torch.argmax's rule (lowest index among equals, the first NaN beats every number), in ONE launch that
+    never writes the nq x nk matrix (mhe_msim_nearest, include/musehip_eval.h).  keys=None is the self mode of metric.py:104-105: the
+    keys are vec itself, `valid` masks both sides and sim(i, i) counts as 0.  valid / keys_valid: [nq] / [nk] masks (bool or int), a
+    masked key is skipped and a masked query row, or one without a candidate, gets -1 (value 0).  Indices are into the rows as given.
+    Returns int32 most [nq]; with return_values also the fp32 similarity of the winner; with return_sim also the [nq, nk] matrix (small
+    sets and tests: NaN where a masked row or column was skipped)."""
+    require_device(vec, keys)
+    self_mode = keys is None
+    assert not (self_mode and keys_valid is not None), "self mode: `valid` masks both sides"
+    vec = vec.to(torch.float32).contiguous()
+    keys = vec if self_mode else keys.to(device=vec.device, dtype=torch.float32).contiguous()
+    assert vec.dim() == 2 and keys.dim() == 2 and vec.shape[1] == 56 and keys.shape[1] == 56, "rows of 56 values (32 | 12 | 12)"
+    nq, nk = vec.shape[0], keys.shape[0]
+    qv = _mask_i32(valid, nq, vec.device)
+    kv = qv if self_mode else _mask_i32(keys_valid, nk, vec.device)
+    most = torch.empty(nq, device=vec.device, dtype=torch.int32)
+    best = torch.empty(nq, device=vec.device, dtype=torch.float32) if return_values else None
+    sim = torch.full((nq, nk), float("nan"), device=vec.device, dtype=torch.float32) if return_sim else None
+    check(lib().mhe_msim_nearest(ptr(vec), nq, ptr(keys), nk, ptr(qv), ptr(kv), int(self_mode), ptr(most), ptr(best), ptr(sim), current_stream()),
+          "mhe_msim_nearest")
+    extra = ([best] if return_values else []) + ([sim] if return_sim else [])
+    return most if not extra else [most] + extra
+
+
+def ONNC_sets(gt_tokens, gen_tokens, gt_lengths=None, gen_lengths=None, valid=None, return_mostsim=False):
+    """The 1NNC of metric.py:83-117 with the two halves as two arguments: gt_tokens [B1, L1] the ground truth, gen_tokens [B2, L2] the
+    generated set.  The get_vectors rows of both go into one [B1 + B2, 56] buffer and one `nearest` call (self mode) classifies every row:
+        onnc = (#valid gt rows whose nearest is a gt row + #valid generated rows whose nearest is a generated row) / #valid rows
+    as an fp32 device scalar (NaN when no row is valid); nothing here syncs with the host.  `valid`: None, one [B] mask for equal
+    halves - applied to both, as run/sample.py:247-252 drops a row from both lists - or a pair (gt mask [B1], generated mask [B2]) for
+    sets of unequal size (a validation split against a generated set).
+    `most` (return_mostsim) holds indices into the UNCOMPACTED concatenation [gt | generated], -1 for a masked row, where the
+    reference's most_sim indexes the compacted list of valid rows; which half each index falls into, and so the count, is the same."""
+    B1, B2 = gt_tokens.shape[0], gen_tokens.shape[0]
+    if gt_tokens.shape[1] == gen_tokens.shape[1] and (gt_lengths is None) == (gen_lengths is None):
+        # rows of one width: the feature kernel is per row and latency bound, so one launch over [gt | generated] gives the same
+        # [B1 + B2, 56] buffer as two launches and a cat, in half the time
+        lengths = None if gt_lengths is None else torch.cat([gt_lengths.to(torch.int32), gen_lengths.to(torch.int32)])
+        vec = get_vectors(torch.cat([gt_tokens.to(torch.int32), gen_tokens.to(torch.int32)]), lengths)
+    else:
+        vec = torch.cat([get_vectors(gt_tokens, gt_lengths), get_vectors(gen_tokens, gen_lengths)])
+    if valid is None:
+        mask = None
+    elif isinstance(valid, (tuple, list)):
+        mask = torch.cat([(valid[0] != 0).reshape(B1), (valid[1] != 0).reshape(B2)])
+    else:
+        assert B1 == B2, "one mask serves both halves only when they are of equal size: pass (gt_valid, gen_valid)"
+        mask = torch.cat([(valid != 0).reshape(B1)] * 2)
+    most = nearest(vec, valid=mask)
+    own = torch.cat([most[:B1] < B1, most[B1:] >= B1]) & (most >= 0)
+    total = mask.sum() if mask is not None else B1 + B2
+    onnc = own.sum() / total
+    return [onnc, most] if return_mostsim else onnc
+
+
+def controllability_counts(metas, tokens, lengths=None, valid=None):
+    """Controllability_Pitch and Controllability_Velocity as device scalars: int64 [4] = (rows, rows whose mean pitch leaves its range,
+    velocity tokens of the rows with a bounded maximum, those outside [min, max]), over the rows where `valid` ([B], default all) is
+    set.  The rules are those of the two functions above; nothing syncs with the host."""
+    c = _counts(metas, tokens, lengths)
+    v = torch.ones(metas.shape[0], device=tokens.device, dtype=torch.bool) if valid is None else (valid != 0)
+    rng = metas[:, 3].long()
+    idx = (rng - 631).clamp(0, 6)
+    lo = torch.where(idx == 0, 3, 27 + 12 * idx).float()        # PITCH_RANGE as arithmetic: no table to copy to the device
+    hi = torch.where(idx == 6, 130, 38 + 12 * idx).float()
+    mean = c[:, 0].float() / c[:, 1].clamp(min=1).float()
+    wrong = (rng != 630) & ~((lo <= mean) & (mean <= hi)) & v
+    use = ((metas[:, 8].long() - 524) != 130) & v
+    zero = torch.zeros((), device=tokens.device, dtype=torch.int64)
+    return torch.stack([v.sum(), wrong.sum(), torch.where(use, c[:, 2].long(), zero).sum(), torch.where(use, c[:, 3].long(), zero).sum()])

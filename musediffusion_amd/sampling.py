@@ -1,12 +1,23 @@
-"""The reference's sampling hot block (run/sample.py:185-220) as two functions: everything between
-"a batch of token ids arrives" and "a batch of token ids leaves", sharded over ranks when a process
-group is initialised.  MIDI decoding / metrics (run/sample.py:222-294) are out of scope."""
+"""The reference's sampling run (run/sample.py:149-317).
+
+`generate` / `modify` are its hot block (:185-220): everything between "a batch of token ids arrives" and "a batch of token ids
+leaves", sharded over ranks when a process group is initialised.  `run_modification` / `run_generation` are the loop around it
+(:168-317): per batch the sampler, ONE decode on the device (utils/decode_util.decode_tokens), the metrics of the batch from that same
+decode (evaluation.evaluate_batch: 1NNC, CP, CV, the running totals - all device scalars) and, when an output directory is given, the
+MIDI files through write_decoded_rows from one device -> host copy.  Without an output directory the modification loop does not sync
+with the host before the final summary.  Not reproduced: tqdm / logger / StringIO plumbing, reading training_args.json, and the
+rank-after-rank decode with its broadcasts (every rank holds the gathered tokens of the global batch and computes the same totals;
+rank 0 writes the files)."""
+import contextlib
+import io
+import os
 from functools import partial
 
 import torch
 
-from . import sharding
+from . import evaluation, sharding
 from .models.rounding import denoised_fn_round
+from .utils import decode_util as du
 
 
 def _prepare(model, cond, device):
@@ -72,3 +83,125 @@ def modify(model, diffusion, cond, step, strength=0.75, clip_denoised=True, top_
     x_noised = diffusion.q_sample(x_start.unsqueeze(-1), timestep, noise=noise, mask=mask3).squeeze(-1)
     tokens = _run(model, diffusion, x_start, mask3, x_noised, step, noising_t, clip_denoised, top_p, clamp_step)
     return sharding.gather_rows(tokens, B) if sharded else tokens
+
+
+# ------------------------------------------------------------------------------------------------ the loop around the hot block
+class SamplingReport:
+    """What a run leaves: total_valid_count (int), totals (evaluation.MetricTotals or None), summary (MetricTotals.summary()'s dict
+    or None), batches (how many the loop ran)."""
+
+    def __init__(self, total_valid_count, totals, summary, batches):
+        self.total_valid_count, self.totals, self.summary, self.batches = total_valid_count, totals, summary, batches
+
+
+def _write_rows(mode, rows, batch_index, previous_count, out_dir, log):
+    """write_decoded_rows with its report going to `log` (the reference: redirect_stdout into the log file and stdout)"""
+    out = io.StringIO()
+    try:
+        with contextlib.redirect_stdout(out):
+            return du.write_decoded_rows(mode, rows, batch_index, previous_count, out_dir, return_indices=True)
+    finally:
+        if out.getvalue():
+            log(out.getvalue())
+
+
+def _fatal_status(rows):
+    """the first status of a DecodedRows on which write_decoded_rows raises, or 0"""
+    for st in rows.status:
+        if int(st) != du.OK and int(st) not in evaluation._INVALID:
+            return int(st)
+    return 0
+
+
+@torch.no_grad()
+def run_modification(model, diffusion, data_loader, *, step, strength=0.75, batch_size, out_dir=None, get_metric=True, sampler=None,
+                     clip_denoised=True, top_p=1, clamp_step=0, log=print):
+    """run/sample.py:168-317 in modification mode.  data_loader yields {'input_ids', 'input_mask'[, 'correct_ids']} for the GLOBAL
+    batch; `sampler(cond)` returns its tokens [B, L] (default: `modify`, sharded when a process group is up).  With get_metric and a
+    'correct_ids' in the batch: evaluation.evaluate_batch (strict validation, as the reference when it computes metrics) and the
+    running totals.  With out_dir: rank 0 writes one file per valid row, named as decode_batch names them (previous_count =
+    batch_index * batch_size), from the same decode - one decode and one device -> host copy per batch - and the metric block of the
+    batch is logged right after it.  Without out_dir nothing is read back until the loop ends: the blocks of all batches are logged
+    then, before the summary, from ONE copy.  Returns a SamplingReport."""
+    if sampler is None:
+        sampler = lambda cond: modify(model, diffusion, cond, step, strength, clip_denoised, top_p, clamp_step, sharded=True)  # noqa: E731
+    write = out_dir is not None and sharding.rank() == 0
+    if write:
+        os.makedirs(out_dir, exist_ok=True)
+    totals, total_valid, pending, batches = None, None, [], 0
+    for batch_index, cond in enumerate(data_loader):
+        tokens = sampler(cond)
+        dev = tokens.device
+        mask = cond["input_mask"].to(dev)
+        metric_on = bool(get_metric) and cond.get("correct_ids") is not None
+        if metric_on:
+            if totals is None:
+                log("### with calculating metrics ...")
+                totals = evaluation.MetricTotals(dev)
+            m = evaluation.evaluate_batch(tokens, cond["correct_ids"].to(dev), mask, strict_validation=True)
+            totals.update(m)
+            dec, count = m.decoded, m.valid_count
+        else:
+            dec = du.decode_tokens(tokens, mask, strict_validation=False)
+            count = (dec.status == du.OK).sum()
+        total_valid = count.clone() if total_valid is None else total_valid + count
+        if out_dir is not None:
+            rows = dec.cpu()
+            if write:
+                _write_rows("modification", rows, batch_index, batch_index * batch_size, out_dir, log)
+            else:
+                evaluation.MetricTotals.raise_if_fatal(_fatal_status(rows))
+            if metric_on:
+                host = m.vector().cpu().tolist()
+                if host[0]:
+                    log(evaluation.batch_block(batch_index, *host[1:]))
+        elif metric_on:
+            pending.append((batch_index, m.vector()))
+        batches += 1
+    if total_valid is None:
+        return SamplingReport(0, None, None, 0)
+    # the one copy of a run without out_dir: [total valid | the seven of MetricTotals.vector() | six per pending batch]
+    parts = [total_valid.double().reshape(1), totals.vector() if totals is not None else torch.zeros(7, device=total_valid.device, dtype=torch.float64)]
+    host = torch.cat(parts + [v for _, v in pending]).cpu().tolist()
+    for n, (batch_index, _) in enumerate(pending):
+        rec = host[8 + 6 * n:14 + 6 * n]
+        if rec[0]:
+            log(evaluation.batch_block(batch_index, *rec[1:]))
+    summary = None
+    if totals is not None:
+        evaluation.MetricTotals.raise_if_fatal(host[7])
+        summary = evaluation.MetricTotals.ratios(host[1:7])
+        log(evaluation.summary_block(summary))
+    if out_dir is not None:
+        log(f"### Written the decoded output to {out_dir}")
+    return SamplingReport(int(host[0]), totals, summary, batches)
+
+
+@torch.no_grad()
+def run_generation(model, diffusion, midi_meta_dict, *, batch_size, seq_len, num_samples, step=None, out_dir, sampler=None,
+                   max_batches=None, clip_denoised=True, top_p=1, clamp_step=0, log=print, device="cuda"):
+    """run/sample.py:168-317 in generation mode: ONE meta_to_batch, sampled again and again (infinite_loader_from_single); every batch
+    is decoded without strict validation and its valid rows are written as generated_{n:0>7}.midi, n counting on from the running
+    total_valid_count (out_dir None: decoded and counted, nothing written).  The loop stops after the batch that reaches num_samples
+    - like the reference it may write more than num_samples files.  max_batches is an addition: the reference loops forever when no
+    row is ever valid.  `sampler(cond)` defaults to `generate`, sharded when a process group is up.  Returns a SamplingReport."""
+    if sampler is None:
+        sampler = lambda cond: generate(model, diffusion, cond, step, clip_denoised, top_p, clamp_step, sharded=True)  # noqa: E731
+    cond = du.meta_to_batch(midi_meta_dict, batch_size, seq_len, device)
+    write = out_dir is not None and sharding.rank() == 0
+    if write:
+        os.makedirs(out_dir, exist_ok=True)
+    total, batch_index = 0, 0
+    while total < num_samples and (max_batches is None or batch_index < max_batches):
+        tokens = sampler(cond)
+        rows = du.decode_tokens(tokens, cond["input_mask"].to(tokens.device), strict_validation=False).cpu()
+        if write:
+            valid_count, _ = _write_rows("generation", rows, batch_index, total, out_dir, log)
+        else:
+            evaluation.MetricTotals.raise_if_fatal(_fatal_status(rows))
+            valid_count = sum(1 for st in rows.status if int(st) == du.OK)
+        total += valid_count
+        batch_index += 1
+    if out_dir is not None:
+        log(f"### Written the decoded output to {out_dir}")
+    return SamplingReport(total, None, None, batch_index)

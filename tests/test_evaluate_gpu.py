@@ -1,0 +1,444 @@
+"""GPU: the evaluation end of the sampling run on the device.  mhe_msim_nearest through the C ABI (include/musehip_eval.h) at the sizes
+where its handling of a key changes hands - the tile of mhe_nearest_key_tile() rows, the wave's quarter of it, the 64 query rows of a
+block - with sentinel-filled outputs and guard bands, every element of most / best / sim compared; one dataset-scale case judged by
+the float64 acceptance rule of tests/evaluate_ref.py; metric.nearest / ONNC_sets, evaluation.evaluate_batch / MetricTotals and the
+driver loops of sampling against every record of tests/golden/evaluate.npz (the reference's own answers); one pass of each driver
+with the real modify / generate.
+
+Bound (tests/test_evaluate_cpu.py holds the fp32 operation order to half of it): |sim - sim_f64| <= tau (sum |r||r'|)(sum |m||m'|)
+(sum |h||h'|), tau = 58 * 2^-24; an index j is accepted iff sim_f64(i, j) >= (1 - 2 tau) max_j' sim_f64(i, j'), or the NaN rule applies."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+import evaluate_ref as ev  # noqa: E402
+from musediffusion_amd import _lib, evaluation, metric, sampling  # noqa: E402
+from musediffusion_amd.utils import decode_util as du  # noqa: E402
+from test_evaluate_cpu import batches, fixture  # noqa: E402
+
+DEV = "cuda"
+GUARD = 64
+MOST_FILL, BEST_FILL, SIM_FILL = -777, -12345.0, -54321.0
+
+
+def T():
+    return int(_lib.lib().mhe_nearest_key_tile())
+
+
+def size(name):
+    t = T()
+    return {"T-1": t - 1, "T": t, "T+1": t + 1, "2T+1": 2 * t + 1}.get(name) or int(name)
+
+
+SIZES = ["1", "2", "63", "64", "65", "T-1", "T", "T+1", "2T+1", "257"]
+
+
+def guarded(n, dtype, fill):
+    return torch.full((n + 2 * GUARD,), fill, device=DEV, dtype=dtype)
+
+
+def call(q, k=None, q_valid=None, k_valid=None, want_sim=True, rc=0):
+    """mhe_msim_nearest through the C ABI on numpy inputs (k=None: self mode) -> (most, best, sim) numpy; the outputs start
+    sentinel-filled and the guard bands on both sides of each must come back untouched"""
+    self_mode = k is None
+    dq = torch.from_numpy(np.ascontiguousarray(q, np.float32)).to(DEV)
+    dk = dq if self_mode else torch.from_numpy(np.ascontiguousarray(k, np.float32)).to(DEV)
+    nq, nk = dq.shape[0], dk.shape[0]
+    dqv = None if q_valid is None else torch.from_numpy(np.asarray(q_valid, np.int32)).to(DEV)
+    dkv = dqv if self_mode else (None if k_valid is None else torch.from_numpy(np.asarray(k_valid, np.int32)).to(DEV))
+    most, best = guarded(nq, torch.int32, MOST_FILL), guarded(nq, torch.float32, BEST_FILL)
+    sim = guarded(nq * nk, torch.float32, SIM_FILL) if want_sim else None
+    got = _lib.lib().mhe_msim_nearest(dq.data_ptr(), nq, dk.data_ptr(), nk, _lib.ptr(dqv), _lib.ptr(dkv), int(self_mode),
+                                      most.data_ptr() + 4 * GUARD, best.data_ptr() + 4 * GUARD,
+                                      None if sim is None else sim.data_ptr() + 4 * GUARD, _lib.current_stream())
+    assert got == rc, _lib.lib().mh_last_error()
+    torch.cuda.synchronize()
+    for buf, fill in ((most, MOST_FILL), (best, BEST_FILL)) + (((sim, SIM_FILL),) if want_sim else ()):
+        assert (buf[:GUARD] == fill).all() and (buf[-GUARD:] == fill).all(), "guard band written"
+    return (most[GUARD:-GUARD].cpu().numpy(), best[GUARD:-GUARD].cpu().numpy(),
+            sim[GUARD:-GUARD].cpu().numpy().reshape(nq, nk) if want_sim else None)
+
+
+def check(q, k=None, q_valid=None, k_valid=None):
+    """one call, every element of most / best / sim judged -> (most, best, sim)"""
+    self_mode = k is None
+    kk = q if self_mode else k
+    most, best, sim = call(q, k, q_valid, k_valid)
+    nq, nk = len(q), len(kk)
+    qv = np.ones(nq, bool) if q_valid is None else np.asarray(q_valid) != 0
+    kv = qv if self_mode else (np.ones(nk, bool) if k_valid is None else np.asarray(k_valid) != 0)
+    on = qv[:, None] & kv[None, :]
+    assert (sim[~on] == np.float32(SIM_FILL)).all(), "an entry of a masked row or column was written"
+    s64, bd = ev.sim64(q, kk), ev.bound(q, kk)
+    if self_mode:
+        assert (np.diagonal(sim)[qv] == 0).all() and not np.signbit(np.diagonal(sim)[qv]).any()
+        np.fill_diagonal(s64, 0.0)
+        np.fill_diagonal(bd, 0.0)
+    assert np.array_equal(np.isnan(sim[on]), np.isnan(s64[on]))
+    fin = on & ~np.isnan(s64)
+    assert (np.abs(sim[fin].astype(np.float64) - s64[fin]) <= bd[fin]).all(), float((np.abs(sim[fin] - s64[fin]) - bd[fin]).max())
+    # the selection: exactly argmax's rule on the kernel's own values, and acceptable by the float64 matrix
+    want_most, want_best = ev.select(np.where(on, sim, np.float32(0)), qv, kv)
+    assert np.array_equal(most, want_most), np.flatnonzero(most != want_most)[:8]
+    assert np.array_equal(best, want_best, equal_nan=True) and np.array_equal(np.signbit(best), np.signbit(want_best))
+    assert not ev.accepted(ev.sim64(q, kk), most, qv, kv, self_mode)
+    return most, best, sim
+
+
+def vectors(n, seed):
+    return ev.unit_vectors(np.random.default_rng(seed), n)
+
+
+# ------------------------------------------------------------------------------------------------ the kernel through the C ABI
+@pytest.mark.parametrize("name", SIZES)
+def test_self_mode_sizes(name):
+    n = size(name)
+    v = vectors(n, 100 + n)
+    most, best, _ = check(v)
+    if n == 1:
+        assert most.tolist() == [0] and best.tolist() == [0.0]          # the diagonal alone wins
+    again = call(v)
+    first = call(v)
+    assert all(np.array_equal(a.view(np.int32), b.view(np.int32)) for a, b in zip(first, again)), "the same call, other bits"
+
+
+@pytest.mark.parametrize("nq,nk", list(zip(SIZES, reversed(SIZES))) + [("1", "1"), ("65", "T+1")])
+def test_two_set_mode_sizes(nq, nk):
+    nq, nk = size(nq), size(nk)
+    q, k = vectors(nq, 7 * nq + nk), vectors(nk, 11 * nk + nq)
+    _, _, sim = check(q, k)
+    if nq > 3:                                # another launch geometry for the same pairs: the bits are the same
+        _, _, part = call(q[3:], k)
+        assert np.array_equal(part.view(np.int32), sim[3:].view(np.int32))
+
+
+def test_duplicated_keys_on_both_sides_of_the_seams():
+    """the query's own row, placed twice among the keys, is its best match (similarity 1 against at most 1): the lower index wins and the
+    two similarities are bit-equal for every query - across a tile seam, a wave seam, a slice seam, and between two tiles' different quarters"""
+    t = T()
+    q = vectors(70, 1)
+    for a, b in ((t - 1, t), (t // 4 - 1, t // 4), (t // 16 - 1, t // 16), (t // 2 + 3, t + t // 4 + 5), (0, 2 * t), (t - 1, 2 * t)):
+        k = vectors(2 * t + 1, 2)
+        k[a] = k[b] = q[a % 70]
+        most, _, sim = check(q, k)
+        assert most[a % 70] == a and np.array_equal(sim[:, a].view(np.int32), sim[:, b].view(np.int32)), (a, b)
+    v = vectors(2 * t + 1, 3)                  # self mode: row b's best is its copy a, row a's is b (its own diagonal counts as 0)
+    v[t] = v[t - 1]
+    most, _, sim = check(v)
+    assert most[t] == t - 1 and most[t - 1] == t
+    assert np.array_equal(np.delete(sim[:, t], [t - 1, t]).view(np.int32), np.delete(sim[:, t - 1], [t - 1, t]).view(np.int32))
+
+
+def test_rows_orthogonal_to_everything():
+    """a zero harmony part makes every similarity of the row 0: index 0 wins, the diagonal included"""
+    v = vectors(T() + 9, 4)
+    z = v.copy()
+    z[:, 44:] = 0
+    most, best, sim = check(z)
+    assert (most == 0).all() and (best == 0).all() and (sim == 0).all()
+    v[[0, 5, 64, T()], 44:] = 0               # orthogonal rows among others: they pick 0, nobody picks them unless all else is 0
+    most, best, _ = check(v)
+    assert most[[0, 5, 64, T()]].tolist() == [0, 0, 0, 0] and (best[[0, 5, 64, T()]] == 0).all()
+    most, _, _ = check(v[:7], z)
+    assert (most == 0).all()
+
+
+def test_nan_rows_as_keys_and_as_queries():
+    t = T()
+    k = vectors(2 * t + 1, 5)
+    k[[t + 2, 7, 2 * t], 44:] = np.nan       # the reference's 0 / 0 harmony vector of a row without notes
+    q = vectors(66, 6)
+    most, best, _ = check(q, k)
+    assert (most == 7).all() and np.isnan(best).all()                      # a NaN beats every number, the first NaN wins
+    kv = np.ones(2 * t + 1, np.int32)
+    kv[7] = 0
+    assert (check(q, k, k_valid=kv)[0] == t + 2).all()
+    q[[0, 65]] = np.nan
+    most, _, _ = check(q, vectors(t + 1, 7))
+    assert most[0] == 0 and most[65] == 0                                  # a NaN query: every similarity is NaN, the first key wins
+    v = vectors(t + 1, 8)
+    v[[0, 70], 44:] = np.nan
+    most, best, _ = check(v)                                               # self mode: the diagonal of a NaN row is the number 0
+    assert most[0] == 1 and most[70] == 0 and most[1] == 0 and most[t] == 0 and np.isnan(best).all()
+
+
+def test_validity_masks():
+    t = T()
+    n = 2 * t + 1
+    v, q = vectors(n, 9), vectors(67, 10)
+    most, best, _ = check(v, q_valid=np.zeros(n, np.int32))                # none valid
+    assert (most == -1).all() and (best == 0).all()
+    one = np.zeros(n, np.int32)
+    one[t] = 1
+    most, best, _ = check(v, q_valid=one)                                  # one valid: its own diagonal is its only candidate
+    assert most[t] == t and best[t] == 0 and (np.delete(most, t) == -1).all()
+    most, _, _ = check(q, v, k_valid=one)
+    assert (most == t).all()
+    most, _, _ = check(q, v, k_valid=np.zeros(n, np.int32))
+    assert (most == -1).all()
+    alt = (np.arange(n) % 2).astype(np.int32)
+    most, _, _ = check(v, q_valid=alt)
+    assert (most[alt == 0] == -1).all() and (most[alt == 1] % 2 == 1).all()
+    check(q, v, q_valid=(np.arange(67) % 3 > 0).astype(np.int32), k_valid=alt)
+    tile = np.ones(n, np.int32)
+    tile[t:2 * t] = 0                                                      # a whole tile invalid
+    most, _, _ = check(v, q_valid=tile)
+    assert (most[t:2 * t] == -1).all() and not ((most >= t) & (most < 2 * t)).any()
+    most, _, _ = check(q, v, k_valid=tile)
+    assert not ((most >= t) & (most < 2 * t)).any()
+    tile[:] = 0
+    tile[2 * t] = tile[t - 1] = 1                                          # two tiles invalid, candidates in the first and the last only
+    assert set(check(q, v, k_valid=tile)[0].tolist()) <= {t - 1, 2 * t}
+
+
+def test_self_mode_needs_one_set():
+    L = _lib.lib()
+    a, b = torch.zeros(4, 56, device=DEV), torch.zeros(4, 56, device=DEV)
+    most, mask = torch.zeros(4, device=DEV, dtype=torch.int32), torch.ones(4, device=DEV, dtype=torch.int32)
+    for args in ((a, 4, b, 4, None, None), (a, 4, a, 3, None, None), (a, 4, a, 4, mask, None)):
+        rc = L.mhe_msim_nearest(args[0].data_ptr(), args[1], args[2].data_ptr(), args[3], _lib.ptr(args[4]), _lib.ptr(args[5]), 1,
+                                most.data_ptr(), None, None, _lib.current_stream())
+        assert rc == _lib.MH_ERR_INVALID and b"self = 1" in L.mh_last_error()
+    assert L.mhe_msim_nearest(a.data_ptr(), 4, a.data_ptr(), 4, mask.data_ptr(), mask.data_ptr(), 1, most.data_ptr(), None, None,
+                              _lib.current_stream()) == 0
+    torch.cuda.synchronize()
+    assert most.tolist() == [0, 0, 0, 0]
+
+
+def test_dataset_scale_against_float64():
+    """4096 x 4096, no matrix written: every index judged by the float64 matrix on the host; and a two-set call with unaligned keys"""
+    v = vectors(4096, 11)
+    most, best, _ = call(v, want_sim=False)
+    s64 = ev.sim64(v, v)
+    assert not ev.accepted(s64, most, self_mode=True)
+    np.fill_diagonal(s64, 0.0)
+    top = s64.max(1)
+    assert (np.abs(best - top) <= 4 * ev.TAU * top).all()         # the accepted index is within 2 tau of the top, its fp32 value within tau of itself
+    # the number of query rows per block follows nq (64 from 64 x CUs rows on, 16 for a small set): the same pairs, the same bits
+    big = np.tile(v, (5, 1))[:64 * 256 + 70]
+    most_big, best_big, _ = call(big, v[:300], want_sim=False)
+    most_few, best_few, _ = call(big[4000:4100], v[:300], want_sim=False)
+    assert np.array_equal(most_big[4000:4100], most_few) and np.array_equal(best_big[4000:4100].view(np.int32), best_few.view(np.int32))
+    assert np.array_equal(most_big[:4096], most_big[4096:8192]) and not ev.accepted(ev.sim64(v, v[:300]), most_big[:4096])
+    flat = torch.from_numpy(np.concatenate([np.zeros(1, np.float32), v[:1000].ravel()])).to(DEV)
+    keys = flat[1:].view(1000, 56)                                         # a key base that is not 16-byte aligned
+    assert keys.data_ptr() % 16 == 4
+    got = metric.nearest(torch.from_numpy(v[1000:1100]).to(DEV), keys)
+    assert not ev.accepted(ev.sim64(v[1000:1100], v[:1000]), got.cpu().numpy())
+
+
+# ------------------------------------------------------------------------------------------------ metric.nearest / ONNC_sets
+def dev(a, dtype=None):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV) if dtype is None else torch.from_numpy(np.ascontiguousarray(a)).to(DEV, dtype)
+
+
+def test_nearest_wrapper_on_the_fixture_vectors():
+    for b in batches():
+        if not b["valid_count"]:
+            continue
+        vec = b["vec"]
+        want, want_best, want_sim = ev.nearest(vec)
+        most, best, sim = metric.nearest(dev(vec), return_values=True, return_sim=True)
+        assert most.dtype == torch.int32 and np.array_equal(most.cpu().numpy(), want)
+        assert np.array_equal(most.cpu().numpy(), b["most"])               # the reference's own most_sim (all rows valid here)
+        assert np.allclose(sim.cpu().numpy(), want_sim, rtol=1e-6, atol=0, equal_nan=True)
+        assert np.allclose(best.cpu().numpy(), want_best, rtol=1e-6, atol=0, equal_nan=True)
+        half = len(vec) // 2
+        mask = np.arange(len(vec)) % 3 > 0
+        got = metric.nearest(dev(vec[:half]), dev(vec[half:]), valid=dev(mask[:half]), keys_valid=dev(mask[half:]))
+        assert np.array_equal(got.cpu().numpy(), ev.nearest(vec[:half], vec[half:], mask[:half], mask[half:])[0])
+        assert np.array_equal(metric.nearest(dev(vec), valid=dev(mask)).cpu().numpy(), ev.nearest(vec, q_valid=mask)[0])
+
+
+def test_onnc_sets_against_the_gemm_path_and_with_unequal_halves():
+    for b in batches():
+        if not b["valid_count"]:
+            continue
+        v = b["valid"]
+        gt, gt_len, _, st1 = du.split_meta_midi(dev(b["correct"][v]), dev(b["mask"][v]))
+        gen, gen_len, _, st2 = du.split_meta_midi(dev(b["sample"][v]), dev(b["mask"][v]))
+        assert not st1.any() and not st2.any()
+        onnc, most = metric.ONNC_sets(gt, gen, gt_len, gen_len, return_mostsim=True)
+        old, old_most = metric.ONNC(torch.cat([gt, gen]), torch.cat([gt_len, gen_len]), return_mostsim=True)
+        assert onnc.dtype == torch.float32 and onnc.dim() == 0 and float(onnc) == float(old) == float(b["onnc"])
+        assert np.array_equal(most.cpu().numpy(), old_most.cpu().numpy()) and np.array_equal(most.cpu().numpy(), b["most"])
+        w = int(gen_len.max())                                             # halves of two widths take the two-launch path: the same answer
+        onnc_w, most_w = metric.ONNC_sets(gt, gen[:, :w].contiguous(), gt_len, gen_len, return_mostsim=True)
+        assert w < gen.shape[1] and torch.equal(onnc_w, onnc) and torch.equal(most_w, most)
+        # unequal halves, one mask per set: the restatement on the device's own vectors
+        n1 = 5
+        m1, m2 = np.arange(n1) != 2, np.arange(len(gen)) % 4 != 1
+        onnc, most = metric.ONNC_sets(gt[:n1], gen, gt_len[:n1], gen_len, valid=(dev(m1), dev(m2)), return_mostsim=True)
+        vec = torch.cat([metric.get_vectors(gt[:n1], gt_len[:n1]), metric.get_vectors(gen, gen_len)]).cpu().numpy()
+        mask = np.concatenate([m1, m2])
+        want = ev.nearest(vec, q_valid=mask)[0]
+        assert np.array_equal(most.cpu().numpy(), want)
+        own = ((want[:n1] >= 0) & (want[:n1] < n1)).sum() + (want[n1:] >= n1).sum()
+        assert float(onnc) == float(np.float32(own) / np.float32(mask.sum()))
+        with pytest.raises(AssertionError):
+            metric.ONNC_sets(gt[:n1], gen, gt_len[:n1], gen_len, valid=dev(m2))
+
+
+# ------------------------------------------------------------------------------------------------ evaluate_batch / MetricTotals
+def library_launches(fn):
+    """the kernels the library launched while fn ran, from its launch recorder"""
+    L = _lib.lib()
+    torch.cuda.synchronize()
+    assert L.mh_profile_start() == 0
+    try:
+        fn()
+    finally:
+        buf = ctypes.create_string_buffer(1 << 16)
+        need = L.mh_profile_stop(buf, len(buf))
+    assert 0 < need <= len(buf)
+    return [ln.split("\t")[0] for ln in buf.value.decode().splitlines() if ln]
+
+
+def test_evaluate_batch_and_totals_reproduce_every_record():
+    totals = evaluation.MetricTotals(DEV)
+    for n, b in enumerate(batches()):
+        before = totals.vector().cpu().tolist()
+        m = evaluation.evaluate_batch(dev(b["sample"]), dev(b["correct"]), dev(b["mask"]))
+        totals.update(m)
+        assert np.array_equal(m.valid.cpu().numpy(), b["valid"]) and int(m.valid_count) == b["valid_count"] and int(m.fatal) == 0
+        assert m.onnc.dtype == torch.float32 and m.valid_count.dtype == torch.int64 and m.counts.dtype == torch.int64
+        after = totals.vector().cpu().tolist()
+        if b["valid_count"]:
+            assert float(m.onnc) == float(b["onnc"]), (n, float(m.onnc))
+            assert np.array_equal(m.most.cpu().numpy(), ev.uncompact(b["most"], b["valid"])), n
+            assert tuple(m.counts.tolist()) == b["cp"] + b["cv"], n
+        else:
+            assert np.isnan(float(m.onnc)) and m.counts.tolist() == [0, 0, 0, 0] and (m.most == -1).all()
+            assert after == before, "a batch without a valid row leaves the totals unchanged"
+        assert after[1:6] == [float(x) for x in b["totals"][1:]] and after[6] == 0, (n, after)
+        assert abs(after[0] - b["totals"][0]) <= (n + 1) * 2.0 ** -23 * abs(b["totals"][0]), (n, after[0])
+    assert totals.onnc_sum.dtype == torch.float32 and totals.onnc_count.dtype == torch.int64
+    s, ref = totals.summary(), fixture()["summary"]
+    assert set(s) == {"onnc", "cp", "cv", "valid"} and all(isinstance(x, float) for x in s.values()) and s["valid"] == 38
+    assert abs(s["onnc"] - ref[0]) <= 5 * 2.0 ** -23 * ref[0]
+    assert abs(s["cp"] - ref[1]) <= 2.0 ** -24 * ref[1] and abs(s["cv"] - ref[2]) <= 2.0 ** -24 * ref[2]
+
+
+def test_launch_count_does_not_depend_on_the_batch_size():
+    b = batches()[1]
+    counts = {}
+    for B in (2, 24):
+        args = (dev(b["sample"][:B]), dev(b["correct"][:B]), dev(b["mask"][:B]))
+        evaluation.evaluate_batch(*args)                                   # warm
+        counts[B] = library_launches(lambda: evaluation.evaluate_batch(*args))
+    assert sorted(counts[2]) == sorted(counts[24]) and len([k for k in counts[24] if k.startswith("msim_nearest_kernel")]) == 1, counts
+    assert not [k for k in counts[24] if "gemm" in k.lower()], "the fused kernel replaces the GEMM path"
+
+
+def test_fatal_status_is_carried_to_the_summary():
+    b = batches()[0]
+    sample = b["sample"].copy()
+    sample[0, 2] = 640                                                     # a time-signature token out of range: BAD_META
+    m = evaluation.evaluate_batch(dev(sample), dev(b["correct"]), dev(b["mask"]))
+    assert int(m.fatal) == du.BAD_META and not bool(m.valid[0])
+    with pytest.raises(KeyError):
+        evaluation.MetricTotals(DEV).update(m).summary()
+
+
+# ------------------------------------------------------------------------------------------------ the drivers
+def fixture_loader():
+    for b in batches():
+        yield {"input_ids": torch.from_numpy(b["correct"]), "input_mask": torch.from_numpy(b["mask"]), "correct_ids": torch.from_numpy(b["correct"])}
+
+
+def test_run_modification_over_the_fixture(tmp_path):
+    f, bs = fixture(), batches()
+    samples = iter([dev(b["sample"]) for b in bs])
+    log = []
+    rep = sampling.run_modification(None, None, fixture_loader(), step=100, batch_size=int(f["batch_size"]), out_dir=str(tmp_path / "mod"),
+                                    sampler=lambda cond: next(samples), log=log.append)
+    assert sorted(os.listdir(tmp_path / "mod")) == sorted(str(x) for x in f["names"]) and len(f["names"]) == 38
+    assert rep.total_valid_count == 38 and rep.batches == 4
+    want = f["totals"][-1]
+    got = rep.totals.vector().cpu().tolist()
+    assert got[1:6] == [float(x) for x in want[1:]] and abs(got[0] - want[0]) <= 4 * 2.0 ** -23 * want[0]
+    ref = f["summary"]
+    assert abs(rep.summary["onnc"] - ref[0]) <= 5 * 2.0 ** -23 * ref[0] and abs(rep.summary["cp"] - ref[1]) <= 2.0 ** -24 * ref[1]
+    assert abs(rep.summary["cv"] - ref[2]) <= 2.0 ** -24 * ref[2]
+    for b in bs:                                                           # the reference's own printed block, as print() would end it
+        assert (b["printed"] == "") == (b["valid_count"] == 0)
+        assert not b["printed"] or b["printed"] in [ln + "\n" for ln in log], b["printed"]
+    assert evaluation.summary_block(rep.summary) in log
+    # the files are decode_batch's
+    os.makedirs(tmp_path / "one")
+    du.decode_batch("modification", bs[0]["sample"], bs[0]["mask"], 0, 0, str(tmp_path / "one"), strict_validation=True)
+    for name in os.listdir(tmp_path / "one"):
+        assert open(tmp_path / "one" / name, "rb").read() == open(tmp_path / "mod" / name, "rb").read()
+    assert len(os.listdir(tmp_path / "one")) == bs[0]["valid_count"]
+    # without an output directory: the same totals and blocks
+    samples = iter([dev(b["sample"]) for b in bs])
+    log2 = []
+    rep2 = sampling.run_modification(None, None, fixture_loader(), step=100, batch_size=int(f["batch_size"]), sampler=lambda cond: next(samples),
+                                     log=log2.append)
+    assert rep2.totals.vector().cpu().tolist() == got and rep2.summary == rep.summary and rep2.total_valid_count == 38
+    assert [ln for ln in log2 if " Metric" in ln] == [ln for ln in log if " Metric" in ln]
+
+
+def test_run_generation_stops_where_the_recorded_counts_say(tmp_path):
+    f = fixture()
+    counts = f["gen_counts"].tolist()
+    assert counts == [2, 5, 7]
+    trials = iter(dev(f["gen_tokens"]).view(3, 8, -1))
+    rep = sampling.run_generation(None, None, f["gen_prefix"].tolist(), batch_size=8, seq_len=f["gen_tokens"].shape[1], num_samples=6,
+                                  out_dir=str(tmp_path / "gen"), sampler=lambda cond: next(trials), log=lambda s: None)
+    assert rep.total_valid_count == 7 and rep.batches == 2                 # 2, then 2 + 5 >= 6: one file more than asked for
+    assert sorted(os.listdir(tmp_path / "gen")) == [str(x) for x in f["gen_names"][:7]] == ["generated_%07d.midi" % n for n in range(7)]
+    trials = iter(dev(f["gen_tokens"]).view(3, 8, -1))
+    rep = sampling.run_generation(None, None, f["gen_prefix"].tolist(), batch_size=8, seq_len=f["gen_tokens"].shape[1], num_samples=100,
+                                  out_dir=str(tmp_path / "all"), sampler=lambda cond: next(trials), max_batches=3, log=lambda s: None)
+    assert rep.total_valid_count == 14 and rep.batches == 3 and sorted(os.listdir(tmp_path / "all")) == [str(x) for x in f["gen_names"]]
+
+
+def _fatal(tokens, mask, strict):
+    st = du.decode_tokens(tokens, mask, strict).status.cpu().tolist()
+    return any(s != du.OK and s not in evaluation._INVALID for s in st)
+
+
+def test_drivers_with_the_real_samplers(tmp_path, monkeypatch):
+    """one pass of each loop with the default sampler on the tiny oracle model, two batches: the tokens are garbage and mostly invalid,
+    which is the point - the loop ends, max_batches holds, the totals are numbers.  A row on which the reference's decode raises
+    (a fatal status) must raise here too: the test decodes the tokens the sampler returned itself to know which of the two to expect."""
+    from test_diffusion_gpu import build
+    m, diff, _, inp, c = build("tiny")
+    diff.noise_fn, diff.rng_mode = None, "philox"
+    torch.manual_seed(11)
+    seen = []
+    for name in ("modify", "generate"):
+        real = getattr(sampling, name)
+        monkeypatch.setattr(sampling, name, lambda *a, _real=real, **k: seen.append(_real(*a, **k)) or seen[-1])
+    batch = inp["batch"]
+    conds = [{"input_ids": batch["input_ids"], "input_mask": batch["input_mask"], "correct_ids": batch["correct_ids"]}] * 2
+    try:
+        rep = sampling.run_modification(m, diff, conds, step=20, batch_size=c["B"], log=lambda s: None)
+    except (IndexError, KeyError, RuntimeError):
+        rep = None
+    assert len(seen) == 2 and all(t.shape == (c["B"], c["L"]) for t in seen)
+    mask = batch["input_mask"].to(DEV)
+    if any(_fatal(t, mask, True) for t in seen):
+        assert rep is None
+    else:
+        host = rep.totals.vector().cpu().tolist()
+        assert rep.batches == 2 and all(np.isfinite(host)) and host[1] == rep.total_valid_count <= 2 * c["B"] and host[6] == 0
+    del seen[:]
+    meta = batch["correct_ids"][0, :11].tolist()
+    try:
+        rep = sampling.run_generation(m, diff, meta, batch_size=c["B"], seq_len=c["L"], num_samples=1000, step=10, out_dir=str(tmp_path / "g"),
+                                      max_batches=2, log=lambda s: None)
+    except (IndexError, KeyError, RuntimeError):
+        rep = None
+    cond = du.meta_to_batch(meta, c["B"], c["L"])
+    assert 1 <= len(seen) <= 2
+    if any(_fatal(t, cond["input_mask"], False) for t in seen):
+        assert rep is None
+    else:
+        assert rep.batches == 2 and len(seen) == 2 and rep.total_valid_count == len(os.listdir(tmp_path / "g")) <= 2 * c["B"]
