@@ -1,5 +1,5 @@
 """The C ABI as ctypes, read from the headers that define it (include/musehip.h, include/musehip_dbg.h, include/musehip_data.h,
-include/musehip_eval.h).
+include/musehip_eval.h, include/musehip_stats.h).
 
 `load(name)` gives the header's enumerators (name -> int), its structs (name -> ctypes.Structure class) and its prototypes
 (name -> (restype, argtypes)).  The reader knows the C these headers are written in and nothing more: a declaration it does not
@@ -15,7 +15,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__fil
 
 SCALARS = {"int": C.c_int, "unsigned": C.c_uint, "float": C.c_float, "int32_t": C.c_int32, "uint32_t": C.c_uint32,
            "int64_t": C.c_int64, "uint64_t": C.c_uint64, "size_t": C.c_size_t}
-POINTEE_ONLY = {"void", "char", "uint8_t"}     # legal behind a `*`, never by value
+POINTEE_ONLY = {"void", "char", "uint8_t", "double"}     # legal behind a `*`, never by value (double: device float64 buffers)
 # A struct field that points to a known struct is POINTER(struct): a host descriptor the caller links with ctypes.pointer().  The C cannot
 # say that such a pointer is for DEVICE memory, where the caller stores an address instead; those fields are named here and are c_void_p.
 DEVICE_STRUCT_FIELDS = {("mh_step_update", "coef")}

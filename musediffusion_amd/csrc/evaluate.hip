@@ -13,6 +13,7 @@
 // combined in LDS by the full rule.  What a pair (i, j) computes is msim_pair() whatever the geometry.  FP32 VALU and LDS-read bound
 // (56 fused multiply-adds and 14 ds_read_b128 per slice and key), no MFMA shape: a pair's operation order is pinned.
 #include "common.h"
+#include "msim_pair.h"
 
 #include "../../include/musehip_eval.h"
 
@@ -22,24 +23,15 @@ constexpr int TB = 256;
 constexpr int NW = TB / 64;         // waves per block
 constexpr int KT = 128;             // key rows per tile == mhe_nearest_key_tile()
 constexpr int KW = KT / NW;         // key rows per wave and tile
-constexpr int DR = 32, DM = 12, DH = 12, D = DR + DM + DH;
+using msim::D;
 constexpr int LD = 60;              // LDS row stride in floats: 16-byte rows, and (KW / 4) * LD = 480 = 32 mod 64 banks
 constexpr int PRE = KT * D / TB;    // floats of a tile each thread moves
 static_assert(KT * LD * sizeof(float) <= 32 * 1024, "a key tile stays within 32 KiB of LDS");
 static_assert(KT * D % TB == 0 && KT <= TB && LD % 4 == 0 && LD >= D, "staging layout");
 
-// the similarity of one pair: the operation order the header states, whatever wave, slice, tile slot or grid handles the pair
-#pragma clang fp contract(off)
-__device__ __forceinline__ float msim_pair(const float (&qv)[D], const float* __restrict__ kr) {
-  float r = 0.0f, m = 0.0f, h = 0.0f;
-#pragma unroll
-  for (int e = 0; e < DR; ++e) r = __builtin_fmaf(qv[e], kr[e], r);
-#pragma unroll
-  for (int e = 0; e < DM; ++e) m = __builtin_fmaf(qv[DR + e], kr[DR + e], m);
-#pragma unroll
-  for (int e = 0; e < DH; ++e) h = __builtin_fmaf(qv[DR + DM + e], kr[DR + DM + e], h);
-  return (r * m) * h;
-}
+// the similarity of one pair is msim::msim_pair() (msim_pair.h): the operation order the header states, whatever wave, slice, tile slot
+// or grid handles the pair
+using msim::msim_pair;
 
 // torch.argmax's order on (value, index) pairs with index -1 = no candidate: does (a, ja) come before (b, jb)?
 __device__ __forceinline__ bool pair_wins(float a, int ja, float b, int jb) {

@@ -4,7 +4,10 @@
 The reference copies the batch to the host, compacts the valid rows with a boolean index and walks them in Python.  Here the per-row
 decode status is a mask: the fused nearest-neighbour kernel (metric.nearest) and the controllability counters skip masked rows, so no
 row is moved, nothing is read back per batch, and the number of launches does not depend on the batch size.  `MetricTotals.summary()`
-is the one device -> host copy of a run."""
+is the one device -> host copy of a run.
+Generation mode has no ground truth (the reference reports nothing there): `evaluate_generated` and `GenerationTotals`, additions, say
+what needs none - diversity and duplicates from the pair statistics of the generated set (metric.pair_stats), novelty against a corpus
+(metric.nearest), CP and CV - under the same rules: masks instead of compaction, one copy at the summary."""
 import torch
 
 from . import metric
@@ -113,3 +116,102 @@ def summary_block(s):
     onnc, cp, cv = s["onnc"], s["cp"], s["cv"]
     return "\n".join(["", f"{f' Summary: Metric ':=^60}", f"{f' ONNC: {onnc:.6f} ': ^60}", f"{f' CP: {cp:.6f} ': ^60}",
                       f"{f' CV: {cv:.6f} ': ^60}", ("=" * 60) + "\n"])
+
+
+# ------------------------------------------------------------------------------------------ generation mode: no ground truth (additions)
+class GeneratedBatch:
+    """Device results of one generated batch.  valid [B] bool; valid_count int64 scalar; vec fp32 [B, 56] (metric.get_vectors of the
+    restored rows; the vector of an invalid row means nothing and is masked by `valid`); counts int64 [4] = (CP total, CP wrong,
+    CV total, CV wrong) over the valid rows; fatal int32 scalar as in BatchMetrics; decoded: the DecodedBatch all of it came from."""
+
+    def __init__(self, valid, valid_count, vec, counts, fatal, decoded):
+        self.valid, self.valid_count, self.vec, self.counts, self.fatal, self.decoded = valid, valid_count, vec, counts, fatal, decoded
+
+
+def evaluate_generated(sample_tokens, input_mask, strict_validation=False):
+    """What a generated batch [B, L] says without a ground truth -> GeneratedBatch.  One decode_tokens gives the per-row status (valid =
+    status OK; the driver writes its files from the same DecodedBatch); get_vectors runs on the restored rows and
+    controllability_counts takes the validity mask.  No .item(), no compaction: the number of library launches does not depend on B."""
+    dec = du.decode_tokens(sample_tokens, input_mask, strict_validation)
+    valid = dec.status == du.OK
+    fatal = _fatal_of(dec.status, torch.ones_like(valid))
+    vec = metric.get_vectors(dec.restored, dec.lengths)
+    counts = metric.controllability_counts(dec.meta, dec.restored, dec.lengths, valid=valid)
+    return GeneratedBatch(valid, valid.sum(), vec, counts, fatal.to(torch.int32), dec)
+
+
+class GenerationTotals:
+    """What a generation run says about the set it made: are the pieces different from each other (diversity), how many are the same
+    piece twice (duplicates), did the model copy a corpus (novelty, memorised), do they respect the ranges their meta asks for (CP, CV).
+    `update` keeps every batch's vectors, validity mask and group ids on the device (56 floats a row) and adds the counts; `summary` is
+    the one device -> host copy of a run: ONE metric.pair_stats call in self mode over all kept rows and, with a corpus [n, 56]
+    (corpus_valid: its mask), ONE metric.nearest call against it.  With several ranks every rank holds the gathered tokens of the
+    global batch and computes the same totals, as MetricTotals documents.
+    duplicate_threshold: two rows are the same piece when their similarity reaches it.  The default is derived, not tuned: a unit-norm
+    part of length n squared through an fmaf chain is within about (3 n + 6) 2^-24 of 1, which gives 188 * 2^-24 for the three parts
+    and the two multiplies - below 256 * 2^-24 = 2^-16, so identical pieces always count as duplicates."""
+
+    def __init__(self, device="cuda", duplicate_threshold=1 - 2.0 ** -16, corpus=None, corpus_valid=None):
+        self.device, self.duplicate_threshold, self.corpus, self.corpus_valid = device, float(duplicate_threshold), corpus, corpus_valid
+        self.vec, self.valid, self.groups = [], [], []
+        self.counts = torch.zeros(4, device=device, dtype=torch.int64)
+        self.valid_count = torch.zeros((), device=device, dtype=torch.int64)
+        self.fatal = torch.zeros((), device=device, dtype=torch.int32)
+
+    def update(self, m, groups=None):
+        """m: a GeneratedBatch; groups: an integer id per row [B] (only rows of one group are compared; default: one group)"""
+        self.vec.append(m.vec)
+        self.valid.append(m.valid)
+        self.groups.append(torch.zeros(m.vec.shape[0], device=m.vec.device, dtype=torch.int32) if groups is None
+                           else groups.to(device=m.vec.device, dtype=torch.int32))
+        self.counts += m.counts
+        self.valid_count += m.valid_count
+        self.fatal = torch.maximum(self.fatal, m.fatal)
+        return self
+
+    def vector(self):
+        """fp64 [13] on the device: valid rows, sum of count, sum of nan, sum of sum, valid rows with a duplicate, CP total, CP wrong,
+        CV total, CV wrong, fatal status, then with a corpus (else zeros) the sum and the number of the non-NaN best similarities and
+        the valid rows whose best similarity reaches the threshold"""
+        dev = self.valid_count.device
+        zero = torch.zeros((), device=dev, dtype=torch.float64)
+        pair, corp = [zero] * 4, [zero] * 3
+        if self.vec:
+            vec, valid = torch.cat(self.vec), torch.cat(self.valid)
+            st = metric.pair_stats(vec, valid=valid, groups=torch.cat(self.groups), threshold=self.duplicate_threshold)
+            pair = [st.count.sum(), st.nan.sum(), st.sum.sum(), (valid & (st.above > 0)).sum()]
+            if self.corpus is not None:
+                most, best = metric.nearest(vec, keys=self.corpus, valid=valid, keys_valid=self.corpus_valid, return_values=True)
+                found = valid & (most >= 0) & ~torch.isnan(best)
+                corp = [torch.where(found, best.double(), zero).sum(), found.sum(), (found & (best >= self.duplicate_threshold)).sum()]
+        head = [self.valid_count] + pair + list(self.counts) + [self.fatal] + corp
+        return torch.stack([x.double() for x in head])
+
+    def ratios(self, host):
+        """host: vector() as Python numbers -> the summary; a ratio with an empty denominator is NaN"""
+        div = lambda a, b: float(a) / float(b) if b else float("nan")
+        out = {"valid": int(host[0]), "pairs": int(host[1]) // 2, "nan_pairs": int(host[2]) // 2, "diversity": 1 - div(host[3], host[1]),
+               "duplicates": div(host[4], host[0]), "cp": div(host[6], host[5]), "cv": div(host[8], host[7])}
+        if self.corpus is not None:
+            out.update(novelty=1 - div(host[10], host[11]), memorised=div(host[12], host[0]))
+        return out
+
+    def summary(self):
+        """{"valid", "pairs", "nan_pairs", "diversity", "duplicates", "cp", "cv"[, "novelty", "memorised"]}: valid = the valid rows
+        counted; pairs / nan_pairs = the unordered counted pairs whose similarity is a number / NaN; diversity = 1 - mean similarity
+        over the counted pairs; duplicates = valid rows with a partner at or above the threshold / valid rows; cp, cv as in
+        MetricTotals.summary(); with a corpus, novelty = 1 - mean of the non-NaN best similarities against it and memorised = the
+        share of valid rows whose best similarity reaches the threshold.  The one sync of a run; raises what MetricTotals.summary()
+        raises when a batch held a row of a fatal status."""
+        host = self.vector().cpu().tolist()
+        MetricTotals.raise_if_fatal(host[9])
+        return self.ratios(host)
+
+
+def generation_block(s):
+    """the summary of a generation run, in the style of summary_block"""
+    valid, pairs = s["valid"], s["pairs"]
+    lines = ["", f"{' Summary: Generation ':=^60}", f"{f' Valid: {valid} ': ^60}", f"{f' Pairs: {pairs} ': ^60}"]
+    names = (("diversity", "Diversity"), ("duplicates", "Duplicates"), ("cp", "CP"), ("cv", "CV"), ("novelty", "Novelty"), ("memorised", "Memorised"))
+    lines += [f"{f' {label}: {s[key]:.6f} ': ^60}" for key, label in names if key in s]
+    return "\n".join(lines + [("=" * 60) + "\n"])

@@ -4,6 +4,9 @@ The reference walks every sequence token by token in Python (`get_vectors`) and 
 matrices; here one kernel launch extracts the [32 rhythm | 12 melody | 12 harmony] features of all sequences and the
 three similarity matrices come from the library's exact-fp32 MFMA GEMM.
 
+Additions without a reference counterpart: `nearest` / `ONNC_sets` (the fused 1-NN kernel, csrc/evaluate.hip) and `pair_stats` /
+`diversity` (sum and counts over all pairs of a set, csrc/pairstats.hip); neither writes the similarity matrix.
+
 Where this module differs from the reference, on purpose (pinned by tests/test_batch_matrix_gpu.py):
   * get_vectors never raises: status 1 = no BAR token (the reference: IndexError), 2 = a malformed note group or a row that ends
     without terminator (ValueError / IndexError); the vectors of a flagged row mean nothing.
@@ -179,3 +182,55 @@ def controllability_counts(metas, tokens, lengths=None, valid=None):
     use = ((metas[:, 8].long() - 524) != 130) & v
     zero = torch.zeros((), device=tokens.device, dtype=torch.int64)
     return torch.stack([v.sum(), wrong.sum(), torch.where(use, c[:, 2].long(), zero).sum(), torch.where(use, c[:, 3].long(), zero).sum()])
+
+
+# ------------------------------------------------------------------------------------------ pair statistics (csrc/pairstats.hip), additions
+class PairStats:
+    """Per query row over its counted pairs (include/musehip_stats.h): sum fp64 [nq] of the non-NaN similarities, count int32 [nq] of
+    them, nan int32 [nq] of the NaN ones, above int32 [nq] = how many of the counted similarities reach the threshold (None without one)."""
+
+    def __init__(self, sum, count, nan, above):
+        self.sum, self.count, self.nan, self.above = sum, count, nan, above
+
+
+def _group_i32(groups, n, device):
+    if groups is None:
+        return None
+    require_device(groups)
+    assert groups.shape == (n,), "a group id per row"
+    return groups.to(device=device, dtype=torch.int32).contiguous()
+
+
+def pair_stats(vec, keys=None, valid=None, keys_valid=None, groups=None, keys_groups=None, threshold=None):
+    """Sum and counts of the MSIM similarities of every row of vec [nq, 56] with the rows of keys [nk, 56], in ONE launch that never
+    writes the nq x nk matrix (mhs_msim_pair_stats): the similarity is bit for bit the one `nearest` selects from.  The conventions
+    are `nearest`'s: keys=None is the self mode (the keys are vec itself, `valid` and `groups` serve both sides) - but here a row is no
+    pair with itself: the diagonal is left out, not counted as 0.  valid / keys_valid: [nq] / [nk] masks (bool or int); a masked key is
+    skipped, a masked query row gets zeros.  groups / keys_groups: integer ids [nq] / [nk], only pairs of equal ids count (None: one
+    group, id 0).  threshold: a Python float; `above` counts the similarities >= it in fp32.  Returns a PairStats; nothing syncs."""
+    require_device(vec, keys)
+    self_mode = keys is None
+    assert not (self_mode and (keys_valid is not None or keys_groups is not None)), "self mode: `valid` and `groups` serve both sides"
+    vec = vec.to(torch.float32).contiguous()
+    keys = vec if self_mode else keys.to(device=vec.device, dtype=torch.float32).contiguous()
+    assert vec.dim() == 2 and keys.dim() == 2 and vec.shape[1] == 56 and keys.shape[1] == 56, "rows of 56 values (32 | 12 | 12)"
+    nq, nk = vec.shape[0], keys.shape[0]
+    qv = _mask_i32(valid, nq, vec.device)
+    kv = qv if self_mode else _mask_i32(keys_valid, nk, vec.device)
+    qg = _group_i32(groups, nq, vec.device)
+    kg = qg if self_mode else _group_i32(keys_groups, nk, vec.device)
+    total = torch.empty(nq, device=vec.device, dtype=torch.float64)
+    count, nan = (torch.empty(nq, device=vec.device, dtype=torch.int32) for _ in range(2))
+    above = torch.empty(nq, device=vec.device, dtype=torch.int32) if threshold is not None else None
+    check(lib().mhs_msim_pair_stats(ptr(vec), nq, ptr(keys), nk, ptr(qv), ptr(kv), ptr(qg), ptr(kg), int(self_mode),
+                                    float("nan") if threshold is None else float(threshold), ptr(total), ptr(count), ptr(nan), ptr(above),
+                                    current_stream()), "mhs_msim_pair_stats")
+    return PairStats(total, count, nan, above)
+
+
+def diversity(vec, valid=None, groups=None):
+    """How different the rows of a set are from each other: (1 - sum of all counted similarities / number of counted pairs, the
+    per-row mean similarity sum / count), both float64 on the device - a scalar and [n]; NaN where nothing was counted.  One
+    pair_stats launch in self mode; nothing syncs with the host."""
+    st = pair_stats(vec, valid=valid, groups=groups)
+    return 1.0 - st.sum.sum() / st.count.sum().double(), st.sum / st.count.double()

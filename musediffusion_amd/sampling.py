@@ -5,9 +5,10 @@ leaves", sharded over ranks when a process group is initialised.  `run_modificat
 (:168-317): per batch the sampler, ONE decode on the device (utils/decode_util.decode_tokens), the metrics of the batch from that same
 decode (evaluation.evaluate_batch: 1NNC, CP, CV, the running totals - all device scalars) and, when an output directory is given, the
 MIDI files through write_decoded_rows from one device -> host copy.  Without an output directory the modification loop does not sync
-with the host before the final summary.  Not reproduced: tqdm / logger / StringIO plumbing, reading training_args.json, and the
-rank-after-rank decode with its broadcasts (every rank holds the gathered tokens of the global batch and computes the same totals;
-rank 0 writes the files)."""
+with the host before the final summary.  Generation mode has no ground truth; with get_metric it reports what needs none
+(evaluation.evaluate_generated / GenerationTotals: diversity, duplicates, novelty against a corpus, CP, CV).  Not reproduced: tqdm /
+logger / StringIO plumbing, reading training_args.json, and the rank-after-rank decode with its broadcasts (every rank holds the
+gathered tokens of the global batch and computes the same totals; rank 0 writes the files)."""
 import contextlib
 import io
 import os
@@ -87,8 +88,8 @@ def modify(model, diffusion, cond, step, strength=0.75, clip_denoised=True, top_
 
 # ------------------------------------------------------------------------------------------------ the loop around the hot block
 class SamplingReport:
-    """What a run leaves: total_valid_count (int), totals (evaluation.MetricTotals or None), summary (MetricTotals.summary()'s dict
-    or None), batches (how many the loop ran)."""
+    """What a run leaves: total_valid_count (int), totals (evaluation.MetricTotals - a generation run with get_metric:
+    evaluation.GenerationTotals - or None), summary (the totals' summary() dict or None), batches (how many the loop ran)."""
 
     def __init__(self, total_valid_count, totals, summary, batches):
         self.total_valid_count, self.totals, self.summary, self.batches = total_valid_count, totals, summary, batches
@@ -179,22 +180,38 @@ def run_modification(model, diffusion, data_loader, *, step, strength=0.75, batc
 
 @torch.no_grad()
 def run_generation(model, diffusion, midi_meta_dict, *, batch_size, seq_len, num_samples, step=None, out_dir, sampler=None,
-                   max_batches=None, clip_denoised=True, top_p=1, clamp_step=0, log=print, device="cuda"):
+                   max_batches=None, clip_denoised=True, top_p=1, clamp_step=0, log=print, device="cuda", get_metric=False, corpus=None,
+                   duplicate_threshold=None):
     """run/sample.py:168-317 in generation mode: ONE meta_to_batch, sampled again and again (infinite_loader_from_single); every batch
     is decoded without strict validation and its valid rows are written as generated_{n:0>7}.midi, n counting on from the running
     total_valid_count (out_dir None: decoded and counted, nothing written).  The loop stops after the batch that reaches num_samples
     - like the reference it may write more than num_samples files.  max_batches is an addition: the reference loops forever when no
-    row is ever valid.  `sampler(cond)` defaults to `generate`, sharded when a process group is up.  Returns a SamplingReport."""
+    row is ever valid.  `sampler(cond)` defaults to `generate`, sharded when a process group is up.  Returns a SamplingReport.
+    get_metric (an addition: the reference reports nothing about a generated set, having no ground truth): every batch goes through
+    evaluation.evaluate_generated instead of the plain decode - the same decode, from which the files are written as before - and
+    evaluation.GenerationTotals keeps its vectors; after the loop the summary (diversity, duplicates, CP, CV and, with `corpus` =
+    [n, 56] get_vectors rows of a training set, novelty and memorised) is logged and fills the report's totals / summary.
+    duplicate_threshold: GenerationTotals' (None: its default)."""
     if sampler is None:
         sampler = lambda cond: generate(model, diffusion, cond, step, clip_denoised, top_p, clamp_step, sharded=True)  # noqa: E731
     cond = du.meta_to_batch(midi_meta_dict, batch_size, seq_len, device)
     write = out_dir is not None and sharding.rank() == 0
     if write:
         os.makedirs(out_dir, exist_ok=True)
-    total, batch_index = 0, 0
+    total, batch_index, totals = 0, 0, None
     while total < num_samples and (max_batches is None or batch_index < max_batches):
         tokens = sampler(cond)
-        rows = du.decode_tokens(tokens, cond["input_mask"].to(tokens.device), strict_validation=False).cpu()
+        mask = cond["input_mask"].to(tokens.device)
+        if get_metric:
+            if totals is None:
+                log("### with calculating metrics ...")
+                kw = {} if duplicate_threshold is None else {"duplicate_threshold": duplicate_threshold}
+                totals = evaluation.GenerationTotals(tokens.device, corpus=corpus, **kw)
+            m = evaluation.evaluate_generated(tokens, mask, strict_validation=False)
+            totals.update(m)
+            rows = m.decoded.cpu()
+        else:
+            rows = du.decode_tokens(tokens, mask, strict_validation=False).cpu()
         if write:
             valid_count, _ = _write_rows("generation", rows, batch_index, total, out_dir, log)
         else:
@@ -202,6 +219,10 @@ def run_generation(model, diffusion, midi_meta_dict, *, batch_size, seq_len, num
             valid_count = sum(1 for st in rows.status if int(st) == du.OK)
         total += valid_count
         batch_index += 1
+    summary = None
+    if totals is not None:
+        summary = totals.summary()                            # the one copy of the metrics: pair statistics over every kept row
+        log(evaluation.generation_block(summary))
     if out_dir is not None:
         log(f"### Written the decoded output to {out_dir}")
-    return SamplingReport(total, None, None, batch_index)
+    return SamplingReport(total, totals, summary, batch_index)
