@@ -150,6 +150,8 @@ extern "C" int mh_train_layer_fwd(const mh_train_layer* t, mh_stream_t stream) {
   const int B = t->B, L = t->L, H = t->H, F = t->F, nh = t->nh, dh = H / nh;
   const int64_t N = (int64_t)B * L, ld = t->ld;
   MH_CHECK_ARG(ld >= N && ld * (int64_t)(F > 3 * H ? F : 3 * H) * 2 < (1ll << 31), "train_layer: ld must cover the B L rows");
+  const mh_dropout* da = site(t->drop_attn);
+  MH_CHECK_ARG(!da || t->keep_bits, "train_layer_fwd: attention dropout needs keep_bits");   // (before the first launch: an error leaves every buffer as it was)
   const float scale = 1.0f / sqrtf((float)dh);
   bf16* qkv = reinterpret_cast<bf16*>(t->qkv);
   int rc;
@@ -160,8 +162,6 @@ extern "C" int mh_train_layer_fwd(const mh_train_layer* t, mh_stream_t stream) {
     if ((rc = mh_gemm_desc_launch(&d, stream))) return rc;
   }
   if ((rc = mh_head_permute(qkv + 2 * H, t->vt, 3 * H, B, L, nh, dh, 4, MH_BF16, stream))) return rc;
-  const mh_dropout* da = site(t->drop_attn);
-  MH_CHECK_ARG(!da || t->keep_bits, "train_layer_fwd: attention dropout needs keep_bits");
   if (da) rc = mh_attention_stream_fwd_drop(qkv, qkv + H, t->vt, t->ctx, ld, 1, B, L, nh, dh, scale, t->lse, (int64_t)L * 3 * H, dh, 3 * H, da, t->keep_bits,
                                             t->bits_in, stream);
   else rc = mh_attention_stream_fwd_ex(qkv, qkv + H, t->vt, t->ctx, ld, 1, B, L, nh, dh, scale, t->lse, (int64_t)L * 3 * H, dh, 3 * H, stream);
@@ -200,6 +200,8 @@ extern "C" int mh_train_layer_bwd(const mh_train_layer* t, mh_stream_t stream) {
   const int64_t N = (int64_t)B * L, ld = t->ld;
   MH_CHECK_ARG(ld >= N, "train_layer: ld must cover the B L rows");
   MH_CHECK_ARG(t->scratch_bytes >= mh_train_layer_scratch_bytes(B, L, H, F, nh, ld), "train_layer_bwd: scratch too small");
+  // (the forward's rule: without this check a site that is on ran the backward WITHOUT its mask when the bits were missing)
+  MH_CHECK_ARG(!site(t->drop_attn) || t->keep_bits, "train_layer_bwd: attention dropout needs keep_bits");
   const Scratch s = carve(reinterpret_cast<char*>(t->scratch), B, L, H, F, nh, ld);
   hipStream_t st = (hipStream_t)stream;
   const float scale = 1.0f / sqrtf((float)dh);
