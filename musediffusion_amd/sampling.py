@@ -8,7 +8,9 @@ MIDI files through write_decoded_rows from one device -> host copy.  Without an 
 with the host before the final summary.  Generation mode has no ground truth; with get_metric it reports what needs none
 (evaluation.evaluate_generated / GenerationTotals: diversity, duplicates, novelty against a corpus, CP, CV).  Not reproduced: tqdm /
 logger / StringIO plumbing, reading training_args.json, and the rank-after-rank decode with its broadcasts (every rank holds the
-gathered tokens of the global batch and computes the same totals; rank 0 writes the files)."""
+gathered tokens of the global batch and computes the same totals; rank 0 writes the files).
+Not in the reference: `infill` / `run_infill` regenerate a bar range, or single note fields inside it, and keep the rest of the piece -
+a plan and a splice (utils/infill_util.py, csrc/infill.hip) around `generate` / `modify`, which run unchanged under the plan's mask."""
 import contextlib
 import io
 import os
@@ -84,6 +86,28 @@ def modify(model, diffusion, cond, step, strength=0.75, clip_denoised=True, top_
     x_noised = diffusion.q_sample(x_start.unsqueeze(-1), timestep, noise=noise, mask=mask3).squeeze(-1)
     tokens = _run(model, diffusion, x_start, mask3, x_noised, step, noising_t, clip_denoised, top_p, clamp_step)
     return sharding.gather_rows(tokens, B) if sharded else tokens
+
+
+@torch.no_grad()
+def infill(model, diffusion, cond, bars, step=None, strength=1.0, room=0, fields="all", clip_denoised=True, top_p=1, clamp_step=0,
+           sharded=True, noise=None):
+    """Not in the reference: keep the piece, regenerate bars lo <= k < hi (`bars` = (lo, hi) or an int tensor [B, 2]) - all of their
+    notes, with `room` more note slots per bar, or with `fields` ('pitch', ('velocity', 'duration'), ...) only those tokens of their
+    notes.  du.plan_infill makes the row and the mask on the GLOBAL batch; the existing paths run under that mask - strength == 1:
+    `generate` (noise in the region, all steps), else `modify` (q_sample to int(step * strength)); du.splice_infill brings the gathered
+    tokens back: the original tokens outside the region bit for bit, whole notes inside it.  -> (tokens [B, L] int64, du.InfillResult).
+    Decode the tokens with cond['input_mask'], not with the plan's mask.  A row that cannot be planned returns unchanged and says why
+    in the result's status."""
+    device = model.word_embedding.weight.device
+    plan = du.plan_infill(cond["input_ids"].to(device), cond["input_mask"].to(device), bars, room, fields)
+    plan_cond = {"input_ids": plan.tokens, "input_mask": plan.mask}
+    if strength == 1:
+        raw = generate(model, diffusion, plan_cond, step, clip_denoised, top_p, clamp_step, sharded=sharded, noise=noise)
+    else:
+        raw = modify(model, diffusion, plan_cond, step or diffusion.num_timesteps, strength, clip_denoised, top_p, clamp_step,
+                     sharded=sharded, noise=noise)
+    tokens, counts = du.splice_infill(plan, raw)
+    return tokens.to(torch.int64), du.InfillResult(plan, counts)
 
 
 # ------------------------------------------------------------------------------------------------ the loop around the hot block
@@ -176,6 +200,31 @@ def run_modification(model, diffusion, data_loader, *, step, strength=0.75, batc
     if out_dir is not None:
         log(f"### Written the decoded output to {out_dir}")
     return SamplingReport(int(host[0]), totals, summary, batches)
+
+
+@torch.no_grad()
+def run_infill(model, diffusion, data_loader, *, bars, step, strength=1.0, room=0, fields="all", batch_size, out_dir=None, get_metric=True,
+               clip_denoised=True, top_p=1, clamp_step=0, log=print):
+    """run_modification with `infill` as its sampler: every batch is sampled on its 'correct_ids' where present (the piece itself; its
+    'input_ids' are the corrupted copy modification mode starts from), else on 'input_ids', and decoded with the batch's own
+    'input_mask'.  Files, numbering, metric blocks and the SamplingReport are that loop's; the report also carries `infill`: the
+    InfillResult counts summed over the run (rows per status, kept / pads / other / changed), from one more device -> host copy at
+    the end."""
+    acc = []
+
+    def sampler(cond):
+        ids = cond["correct_ids"] if cond.get("correct_ids") is not None else cond["input_ids"]
+        tokens, res = infill(model, diffusion, {"input_ids": ids, "input_mask": cond["input_mask"]}, bars, step, strength, room, fields,
+                             clip_denoised, top_p, clamp_step, sharded=True)
+        acc[:] = [res.vector() if not acc else acc[0] + res.vector()]
+        return tokens
+
+    report = run_modification(model, diffusion, data_loader, step=step, strength=strength, batch_size=batch_size, out_dir=out_dir,
+                              get_metric=get_metric, sampler=sampler, log=log)
+    report.infill = du.InfillResult.describe(acc[0].cpu().tolist() if acc else [0] * 9)
+    log("### Infill: rows %s, region tokens kept %d, pads dropped %d, other dropped %d, changed %d" % (
+        report.infill["rows"], report.infill["kept"], report.infill["pads"], report.infill["other"], report.infill["changed"]))
+    return report
 
 
 @torch.no_grad()

@@ -2,7 +2,8 @@
 decode path from sampled token rows to notes, chord markers and Standard MIDI Files (split_meta_midi / restore_chord /
 validation / commu's word_to_event + write_midi: csrc/decode.hip; the file itself is written by a small host writer here).
 The way in - MetaToSequence, encode_notes, merge_and_mask, encode_batch (utils/encode_util.py, csrc/encode.hip) - is re-exported
-here, where the reference keeps MetaToSequence and meta_to_batch; `read_midi` is `write_midi`'s counterpart."""
+here, where the reference keeps MetaToSequence and meta_to_batch; `read_midi` is `write_midi`'s counterpart.  So are the names of
+utils/infill_util.py (plan_infill, splice_infill: the mask and the splice of a bar-range or per-field infill; csrc/infill.hip)."""
 import os
 import struct
 
@@ -12,6 +13,8 @@ import torch
 from .._lib import check, current_stream, lib, ptr, require_device
 from .encode_util import (EncodedBatch, MetaToSequence, UnprocessableMidiError, chord_slots, encode_batch, encode_notes,  # noqa: F401
                           merge_and_mask)
+from .infill_util import (FIELDS, INFILL_BAD_MASK, INFILL_BAD_RANGE, INFILL_NO_EOS, INFILL_OK, INFILL_OVERFLOW,  # noqa: F401
+                          INFILL_STATUS_MESSAGE, InfillPlan, InfillResult, plan_infill, splice_infill)
 
 
 def meta_to_batch(midi_meta_dict_or_tokens, batch_size, seq_len, device="cuda"):
