@@ -7,7 +7,11 @@ row is moved, nothing is read back per batch, and the number of launches does no
 is the one device -> host copy of a run.
 Generation mode has no ground truth (the reference reports nothing there): `evaluate_generated` and `GenerationTotals`, additions, say
 what needs none - diversity and duplicates from the pair statistics of the generated set (metric.pair_stats), novelty against a corpus
-(metric.nearest), CP and CV - under the same rules: masks instead of compaction, one copy at the summary."""
+(metric.nearest), CP and CV - under the same rules: masks instead of compaction, one copy at the summary.
+`HarmonyTotals`, an addition for every mode, is CH: how the decoded notes fit the chord progression the piece was conditioned on
+(metric.harmony_counts), for the whole piece and, for an infill, inside and outside the regenerated bars."""
+import math
+
 import torch
 
 from . import metric
@@ -206,6 +210,106 @@ class GenerationTotals:
         host = self.vector().cpu().tolist()
         MetricTotals.raise_if_fatal(host[9])
         return self.ratios(host)
+
+
+# ------------------------------------------------------------------------------------------ chord fit of a run (additions)
+def _first_bar_shift(decoded):
+    """int64 [B]: 1 where the first token of the restored row that the decoder keeps (2..559) is not BAR, else 0.  The decoder counts a
+    BAR only behind the row's first kept token, so in such a row the notes in front of the first BAR fill bar 0 and the bar that BAR
+    opens is bar 1, while an infill plan numbers the bars from the first BAR (bar 0) and gives the tokens before it to no bar:
+    a note's start / ticks_per_bar is its infill ordinal plus this shift."""
+    r = decoded.restored
+    idx = torch.arange(r.shape[1], device=r.device).unsqueeze(0)
+    kept = (r >= 2) & (r <= 559) & (idx < decoded.lengths.unsqueeze(1))
+    first = torch.where(kept.any(1), r.gather(1, kept.int().argmax(1, keepdim=True)).squeeze(1), torch.full_like(r[:, 0], 2))
+    return (first != 2).long()
+
+
+class HarmonyTotals:
+    """The chord fit of a run as device integers: the seven sums of metric.harmony_counts (notes, judged, chord tones, scale tones and
+    the three tick sums), the pitch-class histogram and, once `update` was given `bars`, (judged, chord tones) inside and outside that
+    bar range.  One mhh_harmony_counts launch per `update` on the DecodedBatch the loop has anyway; `summary` is the one device -> host
+    copy.  With several ranks every rank holds the gathered tokens and computes the same totals, as MetricTotals documents."""
+
+    def __init__(self, device="cuda"):
+        self.totals = torch.zeros(7, device=device, dtype=torch.int64)
+        self.hist = torch.zeros(12, device=device, dtype=torch.int64)
+        self.region = torch.zeros(2, device=device, dtype=torch.int64)
+        self.rest = torch.zeros(2, device=device, dtype=torch.int64)
+        self.rows = torch.zeros((), device=device, dtype=torch.int64)
+        self.with_bars = False
+
+    def update(self, decoded, valid=None, bars=None):
+        """decoded: a DecodedBatch; valid: [B] mask (default: the rows that decoded); bars: (lo, hi) for every row or an int tensor
+        [B, 2] in the bar ordinals of an infill plan (counted from the first BAR of the note region).  With bars the per-bar table
+        says how the notes of bars lo <= k < hi fit (region) and the rest of the piece is the complement (rest)."""
+        if bars is None:
+            hc = metric.harmony_counts(decoded, valid, 0, return_hist=True)
+        else:
+            # large enough for the batch without asking the device: a bar needs a BAR token (the first may come without one)
+            max_bars = min(metric.HARMONY_MAX_BARS, decoded.restored.shape[1] + 1)
+            hc = metric.harmony_counts(decoded, valid, max_bars, return_hist=True)
+            B, dev = hc.counts.shape[0], hc.counts.device
+            if torch.is_tensor(bars):
+                if tuple(bars.shape) != (B, 2):
+                    raise ValueError("harmony: bars is (lo, hi) or an int tensor [B, 2], got %s" % (tuple(bars.shape),))
+                lohi = bars.to(dev).long()
+            else:
+                lohi = torch.tensor([[int(bars[0]), int(bars[1])]], dtype=torch.int64, device=dev).expand(B, 2)
+            lohi = lohi + _first_bar_shift(decoded).unsqueeze(1)
+            k = torch.arange(max_bars, device=dev).unsqueeze(0)
+            inside = ((k >= lohi[:, :1]) & (k < lohi[:, 1:])).unsqueeze(2)
+            region = torch.where(inside, hc.bars[:, :, 1:3], torch.zeros_like(hc.bars[:, :, 1:3])).sum((0, 1), dtype=torch.int64)
+            self.region += region
+            self.rest += hc.counts[:, 1:3].sum(0, dtype=torch.int64) - region
+            self.with_bars = True
+        self.totals += hc.counts[:, :7].sum(0, dtype=torch.int64)
+        self.hist += hc.hist.sum(0, dtype=torch.int64)
+        self.rows += (hc.status == metric.HARMONY_OK).sum()
+        return self
+
+    def vector(self):
+        """int64 [24] on the device: the seven sums, the histogram (12), region (2), rest (2), the rows counted"""
+        return torch.cat([self.totals, self.hist, self.region, self.rest, self.rows.reshape(1)])
+
+    def ratios(self, host):
+        """host: vector() as Python ints -> the summary; a ratio with an empty denominator is NaN"""
+        div = lambda a, b: float(a) / float(b) if b else float("nan")
+        notes, judged, tones, in_scale, ticks, judged_ticks, tone_ticks = (int(x) for x in host[:7])
+        hist = [int(x) for x in host[7:19]]
+        total, entropy = sum(hist), float("nan")
+        if total:
+            entropy = 0.0
+            for x in hist:
+                if x:
+                    p = float(x) / float(total)
+                    entropy -= p * math.log2(p)
+        out = {"rows": int(host[23]), "notes": notes, "judged": judged, "ch": div(judged - tones, judged),
+               "ch_ticks": div(judged_ticks - tone_ticks, judged_ticks), "out_of_scale": div(notes - in_scale, notes),
+               "judged_share": div(judged, notes), "pitch_class_entropy": entropy}
+        if self.with_bars:
+            region, rest = host[19:21], host[21:23]
+            out.update(ch_region=div(region[0] - region[1], region[0]), ch_rest=div(rest[0] - rest[1], rest[0]),
+                       judged_region=int(region[0]), judged_rest=int(rest[0]))
+        return out
+
+    def summary(self):
+        """{"rows", "notes", "judged", "ch", "ch_ticks", "out_of_scale", "judged_share", "pitch_class_entropy"[, "ch_region", "ch_rest",
+        "judged_region", "judged_rest"]}: rows = the rows counted; ch = judged notes off their chord / judged notes; ch_ticks the same
+        by sounding ticks; out_of_scale = notes outside the key's scale / notes; judged_share = judged / notes; pitch_class_entropy in
+        bits, computed here in float64 from the integer histogram; with bars, ch inside and outside the bar range and the judged notes
+        of each.  The one device -> host copy."""
+        return self.ratios(self.vector().cpu().tolist())
+
+
+def harmony_block(s):
+    """the chord-fit summary of a run, in the style of summary_block"""
+    rows, judged, notes = s["rows"], s["judged"], s["notes"]
+    lines = ["", f"{' Summary: Harmony ':=^60}", f"{f' Rows: {rows} ': ^60}", f"{f' Judged notes: {judged} of {notes} ': ^60}"]
+    names = (("ch", "CH"), ("ch_ticks", "CH by ticks"), ("out_of_scale", "Out of scale"), ("judged_share", "Judged share"),
+             ("pitch_class_entropy", "Pitch-class entropy"), ("ch_region", "CH region"), ("ch_rest", "CH rest"))
+    lines += [f"{f' {label}: {s[key]:.6f} ': ^60}" for key, label in names if key in s]
+    return "\n".join(lines + [("=" * 60) + "\n"])
 
 
 def generation_block(s):

@@ -5,7 +5,9 @@ matrices; here one kernel launch extracts the [32 rhythm | 12 melody | 12 harmon
 three similarity matrices come from the library's exact-fp32 MFMA GEMM.
 
 Additions without a reference counterpart: `nearest` / `ONNC_sets` (the fused 1-NN kernel, csrc/evaluate.hip) and `pair_stats` /
-`diversity` (sum and counts over all pairs of a set, csrc/pairstats.hip); neither writes the similarity matrix.
+`diversity` (sum and counts over all pairs of a set, csrc/pairstats.hip); neither writes the similarity matrix.  `harmony_counts` /
+`Controllability_Harmony` (csrc/harmony.hip) are CH, the control metric of the ComMU paper the reference never wrote: do the notes of
+a decoded piece fit the chord progression it was conditioned on.
 
 Where this module differs from the reference, on purpose (pinned by tests/test_batch_matrix_gpu.py):
   * get_vectors never raises: status 1 = no BAR token (the reference: IndexError), 2 = a malformed note group or a row that ends
@@ -17,7 +19,7 @@ Where this module differs from the reference, on purpose (pinned by tests/test_b
     637) where the reference raises KeyError; a row without pitch tokens counts as wrong, as the reference's NaN mean does."""
 import torch
 
-from ._lib import check, current_stream, lib, ptr, require_device
+from ._lib import HARMONY_ENUMS, check, current_stream, lib, ptr, require_device
 
 
 def get_vectors(tokens, lengths=None, note_len=128, return_status=False):
@@ -234,3 +236,61 @@ def diversity(vec, valid=None, groups=None):
     pair_stats launch in self mode; nothing syncs with the host."""
     st = pair_stats(vec, valid=valid, groups=groups)
     return 1.0 - st.sum.sum() / st.count.sum().double(), st.sum / st.count.double()
+
+
+# ------------------------------------------------------------------------------------------ chord fit (csrc/harmony.hip), additions
+# mirror of enum mhh_status (include/musehip_harmony.h)
+HARMONY_OK, HARMONY_MASKED, HARMONY_BAD_META, HARMONY_BAD_COUNTS = (HARMONY_ENUMS["MHH_" + n] for n in ("OK", "MASKED", "BAD_META", "BAD_COUNTS"))
+HARMONY_COUNT_NAMES = ("notes", "judged", "chord_tones", "scale_tones", "ticks", "judged_ticks", "chord_tone_ticks", "bars_used")
+HARMONY_MAX_NOTES, HARMONY_MAX_CHORDS, HARMONY_MAX_BARS = 32768, 4096, 512
+
+
+class HarmonyCounts:
+    """Device results of one batch (include/musehip_harmony.h): counts int32 [B, 8] in HARMONY_COUNT_NAMES order, status int32 [B]
+    (HARMONY_OK ...; a row that is not OK has zeros everywhere), bars int32 [B, max_bars, 4] = (notes, judged, chord tones, scale
+    tones) of the notes that start in each bar, or None, hist int32 [B, 12] = notes per pitch class, or None."""
+
+    def __init__(self, counts, status, bars, hist):
+        self.counts, self.status, self.bars, self.hist = counts, status, bars, hist
+
+
+def harmony_counts_raw(notes, chords, counts3, meta, valid=None, max_bars=0, return_hist=False):
+    """mhh_harmony_counts on the five tensors a decode leaves: notes [B, max_notes, 4] = (start tick, end tick, pitch, velocity),
+    chords [B, max_chords, 2] = (tick, chord token), counts3 [B, 3] = (notes, chords, -), meta [B, 11], valid [B] or None (every
+    row) -> HarmonyCounts.  Does every note fit the chord in force at its onset and the scale of the piece's key: the rule is the
+    header's.  ONE launch whatever the batch; nothing syncs with the host."""
+    require_device(notes, chords, counts3, meta, valid)
+    max_bars = int(max_bars)
+    if notes.dim() != 3 or notes.shape[2] != 4 or chords.dim() != 3 or chords.shape[2] != 2 or chords.shape[0] != notes.shape[0]:
+        raise ValueError("harmony_counts: notes [B, max_notes, 4] and chords [B, max_chords, 2]")
+    B, max_notes, max_chords = notes.shape[0], notes.shape[1], chords.shape[1]
+    if tuple(counts3.shape) != (B, 3) or tuple(meta.shape) != (B, 11):
+        raise ValueError("harmony_counts: counts [B, 3] and meta [B, 11]")
+    if not (1 <= max_notes <= HARMONY_MAX_NOTES and 1 <= max_chords <= HARMONY_MAX_CHORDS and 0 <= max_bars <= HARMONY_MAX_BARS):
+        raise ValueError("harmony_counts: max_notes in 1..%d, max_chords in 1..%d, max_bars in 0..%d (got %d, %d, %d)" % (
+            HARMONY_MAX_NOTES, HARMONY_MAX_CHORDS, HARMONY_MAX_BARS, max_notes, max_chords, max_bars))
+    dev = notes.device
+    notes, chords, counts3, meta = (t.to(torch.int32).contiguous() for t in (notes, chords, counts3, meta))
+    valid = _mask_i32(valid, B, dev)
+    counts = torch.empty(B, 8, device=dev, dtype=torch.int32)
+    status = torch.empty(B, device=dev, dtype=torch.int32)
+    hist = torch.empty(B, 12, device=dev, dtype=torch.int32) if return_hist else None
+    bars = torch.empty(B, max_bars, 4, device=dev, dtype=torch.int32) if max_bars else None
+    check(lib().mhh_harmony_counts(ptr(notes), ptr(chords), ptr(counts3), ptr(meta), ptr(valid), ptr(counts), ptr(hist), ptr(bars), ptr(status),
+                                   B, max_notes, max_chords, max_bars, current_stream()), "mhh_harmony_counts")
+    return HarmonyCounts(counts, status, bars, hist)
+
+
+def harmony_counts(decoded, valid=None, max_bars=0, return_hist=False):
+    """harmony_counts_raw on a DecodedBatch (utils.decode_util.decode_tokens); valid defaults to the rows that decoded
+    (decoded.status == OK: the lists of the others hold nothing)."""
+    if valid is None:
+        valid = decoded.status == 0
+    return harmony_counts_raw(decoded.notes, decoded.chords, decoded.counts, decoded.meta, valid, max_bars, return_hist)
+
+
+def Controllability_Harmony(decoded, valid=None):
+    """CH, the third control metric beside Controllability_Pitch / _Velocity -> (judged notes, judged notes that are no tone of the
+    chord in force at their onset) of the valid rows, as Python ints (total, wrong)."""
+    c = harmony_counts(decoded, valid).counts[:, 1:3].sum(0, dtype=torch.int64).cpu().tolist()
+    return int(c[0]), int(c[0] - c[1])

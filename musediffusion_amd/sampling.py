@@ -10,7 +10,9 @@ with the host before the final summary.  Generation mode has no ground truth; wi
 logger / StringIO plumbing, reading training_args.json, and the rank-after-rank decode with its broadcasts (every rank holds the
 gathered tokens of the global batch and computes the same totals; rank 0 writes the files).
 Not in the reference: `infill` / `run_infill` regenerate a bar range, or single note fields inside it, and keep the rest of the piece -
-a plan and a splice (utils/infill_util.py, csrc/infill.hip) around `generate` / `modify`, which run unchanged under the plan's mask."""
+a plan and a splice (utils/infill_util.py, csrc/infill.hip) around `generate` / `modify`, which run unchanged under the plan's mask.
+Nor is `harmony=True` of the three loops: the batch's one decode also goes through evaluation.HarmonyTotals (csrc/harmony.hip) and
+the report says how the notes fit the chords the pieces were conditioned on."""
 import contextlib
 import io
 import os
@@ -113,7 +115,8 @@ def infill(model, diffusion, cond, bars, step=None, strength=1.0, room=0, fields
 # ------------------------------------------------------------------------------------------------ the loop around the hot block
 class SamplingReport:
     """What a run leaves: total_valid_count (int), totals (evaluation.MetricTotals - a generation run with get_metric:
-    evaluation.GenerationTotals - or None), summary (the totals' summary() dict or None), batches (how many the loop ran)."""
+    evaluation.GenerationTotals - or None), summary (the totals' summary() dict or None), batches (how many the loop ran).  A run with
+    harmony=True adds `harmony` (evaluation.HarmonyTotals.summary(), or None when no batch ran); run_infill adds `infill`."""
 
     def __init__(self, total_valid_count, totals, summary, batches):
         self.total_valid_count, self.totals, self.summary, self.batches = total_valid_count, totals, summary, batches
@@ -140,20 +143,24 @@ def _fatal_status(rows):
 
 @torch.no_grad()
 def run_modification(model, diffusion, data_loader, *, step, strength=0.75, batch_size, out_dir=None, get_metric=True, sampler=None,
-                     clip_denoised=True, top_p=1, clamp_step=0, log=print):
+                     clip_denoised=True, top_p=1, clamp_step=0, log=print, harmony=False, harmony_bars=None):
     """run/sample.py:168-317 in modification mode.  data_loader yields {'input_ids', 'input_mask'[, 'correct_ids']} for the GLOBAL
     batch; `sampler(cond)` returns its tokens [B, L] (default: `modify`, sharded when a process group is up).  With get_metric and a
     'correct_ids' in the batch: evaluation.evaluate_batch (strict validation, as the reference when it computes metrics) and the
     running totals.  With out_dir: rank 0 writes one file per valid row, named as decode_batch names them (previous_count =
     batch_index * batch_size), from the same decode - one decode and one device -> host copy per batch - and the metric block of the
     batch is logged right after it.  Without out_dir nothing is read back until the loop ends: the blocks of all batches are logged
-    then, before the summary, from ONE copy.  Returns a SamplingReport."""
+    then, before the summary, from ONE copy.  Returns a SamplingReport.
+    harmony (an addition): the DecodedBatch every batch has anyway also goes through evaluation.HarmonyTotals - one more launch per
+    batch, one more device -> host copy after the loop - and the report gains `harmony`, its summary (CH: do the notes fit the chords
+    the piece was conditioned on), logged as evaluation.harmony_block; harmony_bars: HarmonyTotals.update's `bars`."""
     if sampler is None:
         sampler = lambda cond: modify(model, diffusion, cond, step, strength, clip_denoised, top_p, clamp_step, sharded=True)  # noqa: E731
     write = out_dir is not None and sharding.rank() == 0
     if write:
         os.makedirs(out_dir, exist_ok=True)
     totals, total_valid, pending, batches = None, None, [], 0
+    chord_fit = None
     for batch_index, cond in enumerate(data_loader):
         tokens = sampler(cond)
         dev = tokens.device
@@ -170,6 +177,8 @@ def run_modification(model, diffusion, data_loader, *, step, strength=0.75, batc
             dec = du.decode_tokens(tokens, mask, strict_validation=False)
             count = (dec.status == du.OK).sum()
         total_valid = count.clone() if total_valid is None else total_valid + count
+        if harmony:
+            chord_fit = (chord_fit or evaluation.HarmonyTotals(dev)).update(dec, bars=harmony_bars)
         if out_dir is not None:
             rows = dec.cpu()
             if write:
@@ -184,7 +193,10 @@ def run_modification(model, diffusion, data_loader, *, step, strength=0.75, batc
             pending.append((batch_index, m.vector()))
         batches += 1
     if total_valid is None:
-        return SamplingReport(0, None, None, 0)
+        report = SamplingReport(0, None, None, 0)
+        if harmony:
+            report.harmony = None
+        return report
     # the one copy of a run without out_dir: [total valid | the seven of MetricTotals.vector() | six per pending batch]
     parts = [total_valid.double().reshape(1), totals.vector() if totals is not None else torch.zeros(7, device=total_valid.device, dtype=torch.float64)]
     host = torch.cat(parts + [v for _, v in pending]).cpu().tolist()
@@ -199,17 +211,22 @@ def run_modification(model, diffusion, data_loader, *, step, strength=0.75, batc
         log(evaluation.summary_block(summary))
     if out_dir is not None:
         log(f"### Written the decoded output to {out_dir}")
-    return SamplingReport(int(host[0]), totals, summary, batches)
+    report = SamplingReport(int(host[0]), totals, summary, batches)
+    if harmony:
+        report.harmony = chord_fit.summary()
+        log(evaluation.harmony_block(report.harmony))
+    return report
 
 
 @torch.no_grad()
 def run_infill(model, diffusion, data_loader, *, bars, step, strength=1.0, room=0, fields="all", batch_size, out_dir=None, get_metric=True,
-               clip_denoised=True, top_p=1, clamp_step=0, log=print):
+               clip_denoised=True, top_p=1, clamp_step=0, log=print, harmony=False):
     """run_modification with `infill` as its sampler: every batch is sampled on its 'correct_ids' where present (the piece itself; its
     'input_ids' are the corrupted copy modification mode starts from), else on 'input_ids', and decoded with the batch's own
     'input_mask'.  Files, numbering, metric blocks and the SamplingReport are that loop's; the report also carries `infill`: the
     InfillResult counts summed over the run (rows per status, kept / pads / other / changed), from one more device -> host copy at
-    the end."""
+    the end.  harmony: run_modification's, with this run's `bars`: the report's `harmony` also says how the regenerated bars
+    (ch_region) and the kept ones (ch_rest) fit their chords."""
     acc = []
 
     def sampler(cond):
@@ -220,7 +237,7 @@ def run_infill(model, diffusion, data_loader, *, bars, step, strength=1.0, room=
         return tokens
 
     report = run_modification(model, diffusion, data_loader, step=step, strength=strength, batch_size=batch_size, out_dir=out_dir,
-                              get_metric=get_metric, sampler=sampler, log=log)
+                              get_metric=get_metric, sampler=sampler, log=log, harmony=harmony, harmony_bars=bars if harmony else None)
     report.infill = du.InfillResult.describe(acc[0].cpu().tolist() if acc else [0] * 9)
     log("### Infill: rows %s, region tokens kept %d, pads dropped %d, other dropped %d, changed %d" % (
         report.infill["rows"], report.infill["kept"], report.infill["pads"], report.infill["other"], report.infill["changed"]))
@@ -230,7 +247,7 @@ def run_infill(model, diffusion, data_loader, *, bars, step, strength=1.0, room=
 @torch.no_grad()
 def run_generation(model, diffusion, midi_meta_dict, *, batch_size, seq_len, num_samples, step=None, out_dir, sampler=None,
                    max_batches=None, clip_denoised=True, top_p=1, clamp_step=0, log=print, device="cuda", get_metric=False, corpus=None,
-                   duplicate_threshold=None):
+                   duplicate_threshold=None, harmony=False):
     """run/sample.py:168-317 in generation mode: ONE meta_to_batch, sampled again and again (infinite_loader_from_single); every batch
     is decoded without strict validation and its valid rows are written as generated_{n:0>7}.midi, n counting on from the running
     total_valid_count (out_dir None: decoded and counted, nothing written).  The loop stops after the batch that reaches num_samples
@@ -240,14 +257,15 @@ def run_generation(model, diffusion, midi_meta_dict, *, batch_size, seq_len, num
     evaluation.evaluate_generated instead of the plain decode - the same decode, from which the files are written as before - and
     evaluation.GenerationTotals keeps its vectors; after the loop the summary (diversity, duplicates, CP, CV and, with `corpus` =
     [n, 56] get_vectors rows of a training set, novelty and memorised) is logged and fills the report's totals / summary.
-    duplicate_threshold: GenerationTotals' (None: its default)."""
+    duplicate_threshold: GenerationTotals' (None: its default).  harmony: as in run_modification - the batch's one decode also goes
+    through evaluation.HarmonyTotals and the report gains `harmony`."""
     if sampler is None:
         sampler = lambda cond: generate(model, diffusion, cond, step, clip_denoised, top_p, clamp_step, sharded=True)  # noqa: E731
     cond = du.meta_to_batch(midi_meta_dict, batch_size, seq_len, device)
     write = out_dir is not None and sharding.rank() == 0
     if write:
         os.makedirs(out_dir, exist_ok=True)
-    total, batch_index, totals = 0, 0, None
+    total, batch_index, totals, chord_fit = 0, 0, None, None
     while total < num_samples and (max_batches is None or batch_index < max_batches):
         tokens = sampler(cond)
         mask = cond["input_mask"].to(tokens.device)
@@ -258,9 +276,12 @@ def run_generation(model, diffusion, midi_meta_dict, *, batch_size, seq_len, num
                 totals = evaluation.GenerationTotals(tokens.device, corpus=corpus, **kw)
             m = evaluation.evaluate_generated(tokens, mask, strict_validation=False)
             totals.update(m)
-            rows = m.decoded.cpu()
+            dec = m.decoded
         else:
-            rows = du.decode_tokens(tokens, mask, strict_validation=False).cpu()
+            dec = du.decode_tokens(tokens, mask, strict_validation=False)
+        if harmony:
+            chord_fit = (chord_fit or evaluation.HarmonyTotals(tokens.device)).update(dec)
+        rows = dec.cpu()
         if write:
             valid_count, _ = _write_rows("generation", rows, batch_index, total, out_dir, log)
         else:
@@ -274,4 +295,9 @@ def run_generation(model, diffusion, midi_meta_dict, *, batch_size, seq_len, num
         log(evaluation.generation_block(summary))
     if out_dir is not None:
         log(f"### Written the decoded output to {out_dir}")
-    return SamplingReport(total, totals, summary, batch_index)
+    report = SamplingReport(total, totals, summary, batch_index)
+    if harmony:
+        report.harmony = chord_fit.summary() if chord_fit is not None else None
+        if chord_fit is not None:
+            log(evaluation.harmony_block(report.harmony))
+    return report
