@@ -206,6 +206,38 @@ def distance_argmax(x, table, table_sqnorm):
     return idx
 
 
+def note_classes():
+    """mhg_note_classes: the ComMU token ranges [lo, hi) of PAD, EOS, BAR, PITCH, VELOCITY, DURATION, POSITION as 7 pairs."""
+    from ._lib import GrammarClasses
+    d = GrammarClasses()
+    check(lib().mhg_note_classes(C.byref(d)), "mhg_note_classes")
+    return tuple((int(d.lo[c]), int(d.hi[c])) for c in range(7))
+
+
+def class_argmax(x, table, aux, mode=1, classes=None):
+    """The argmax kernels' scores reduced per token class instead of over the whole vocabulary (include/musehip_grammar.h):
+    -> (cls_score [n, 8] fp32, cls_idx [n, 8] int32), slots 0..6 = the best (score, first index) inside each of `classes` (7 pairs
+    [lo, hi); default: note_classes()), slot 7 = the whole vocabulary, whose index is logits_argmax's (mode 1, aux = the bias) /
+    distance_argmax's (mode 2, aux = |W_v|^2) bit for bit.  One launch; the [n, V] scores are never stored."""
+    from ._lib import GrammarClasses
+    x, table, aux = _c(x, torch.float32), _c(table, torch.float32), _c(aux, torch.float32)
+    V, E = table.shape
+    n = x.numel() // E
+    d = GrammarClasses()
+    if classes is None:
+        check(lib().mhg_note_classes(C.byref(d)), "mhg_note_classes")
+    else:
+        if len(classes) != 7:
+            raise ValueError("class_argmax: seven (lo, hi) token ranges, got %d" % len(classes))
+        for c, (lo, hi) in enumerate(classes):
+            d.lo[c], d.hi[c] = int(lo), int(hi)
+    cls_score = torch.empty(n, 8, device=x.device, dtype=torch.float32)
+    cls_idx = torch.empty(n, 8, device=x.device, dtype=torch.int32)
+    check(lib().mhg_class_argmax(ptr(x), ptr(table), ptr(aux), C.byref(d), ptr(cls_score), ptr(cls_idx), n, E, V, int(mode),
+                                 current_stream()), "mhg_class_argmax")
+    return cls_score, cls_idx
+
+
 def distance_ce_fwd(dots, w_sqnorm, x_sqnorm, ids32, V):
     """dots [n, ld] fp32 -> (nll [n], lse [n]) of the logits_mode 2 scores against ids32 [n] int32."""
     n, ld = dots.shape

@@ -12,7 +12,9 @@ gathered tokens of the global batch and computes the same totals; rank 0 writes 
 Not in the reference: `infill` / `run_infill` regenerate a bar range, or single note fields inside it, and keep the rest of the piece -
 a plan and a splice (utils/infill_util.py, csrc/infill.hip) around `generate` / `modify`, which run unchanged under the plan's mask.
 Nor is `harmony=True` of the three loops: the batch's one decode also goes through evaluation.HarmonyTotals (csrc/harmony.hip) and
-the report says how the notes fit the chords the pieces were conditioned on."""
+the report says how the notes fit the chords the pieces were conditioned on.  Nor is `constrained=True` of `generate` / `modify` and of the
+loops: the final argmax becomes the best token sequence the decode path accepts (utils/grammar_util.py, csrc/grammar.hip), so that a
+row is not lost to one token in the wrong place; the in-loop clamp (denoised_fn_round) stays as it is."""
 import contextlib
 import io
 import os
@@ -22,7 +24,7 @@ import torch
 
 from . import evaluation, sharding
 from .models.rounding import denoised_fn_round
-from .utils import decode_util as du
+from .utils import decode_util as du, grammar_util as gu
 
 
 def _prepare(model, cond, device):
@@ -33,7 +35,7 @@ def _prepare(model, cond, device):
     return x_start, mask3
 
 
-def _run(model, diffusion, x_start, mask3, x_noised, step, noising_t, clip_denoised, top_p, clamp_step):
+def _run(model, diffusion, x_start, mask3, x_noised, step, noising_t, clip_denoised, top_p, clamp_step, constrain=None):
     T = diffusion.num_timesteps
     if step == T:                                                                 # sample.py:109-114
         gap, sample_fn = 1, diffusion.p_sample_loop
@@ -45,17 +47,40 @@ def _run(model, diffusion, x_start, mask3, x_noised, step, noising_t, clip_denoi
                         denoised_fn=partial(denoised_fn_round, emb, dist=None), model_kwargs={}, top_p=top_p,
                         clamp_step=clamp_step, clamp_first=True, mask=mask3, x_start=x_start, gap=gap,
                         t_enc=noising_t, only_last=True)                          # sample.py:200-215
-    return model.argmax_tokens(samples[-1])                                       # sample.py:218-220
+    if constrain is None:
+        return model.argmax_tokens(samples[-1])                                   # sample.py:218-220
+    return model.argmax_tokens(samples[-1], constrain=constrain)                  # -> (tokens, ConstrainResult)
+
+
+def _constrain_args(local, bars, B, sharded):
+    """argmax_tokens' `constrain` for this rank's rows: a per-row bars tensor [B, 2] of the GLOBAL batch is cut like the batch"""
+    if isinstance(bars, torch.Tensor):
+        lo, hi = sharding.shard_bounds(B) if sharded else (0, B)
+        bars = bars[lo:hi]
+    return local["input_ids"], local["input_mask"], bars
+
+
+def _gather(out, B, sharded, constrained):
+    """the local shard's tokens - with `constrained` (tokens, ConstrainResult), every tensor of it - gathered to the global batch"""
+    if not constrained:
+        return sharding.gather_rows(out, B) if sharded else out
+    tokens, res = out
+    if sharded:
+        tokens = sharding.gather_rows(tokens, B)
+        res = gu.ConstrainResult(*(sharding.gather_rows(t, B) for t in (res.status, res.path_score, res.counts)))
+    return tokens, res
 
 
 @torch.no_grad()
 def generate(model, diffusion, cond, step=None, clip_denoised=True, top_p=1, clamp_step=0, sharded=True, noise=None,
-             t_enc=None):
+             t_enc=None, constrained=False, bars="exact"):
     """Generation mode: noise everywhere except the anchored meta prefix (run/sample.py:190-193).
     `cond` = {'input_ids', 'input_mask'} for the GLOBAL batch; returns int64 tokens [B, L] on every rank.
     Additions to the reference's block: `noise` = the start latent's draw for the GLOBAL batch (each rank takes its rows;
     default: this rank's `torch.randn_like`, as the reference), `t_enc` = stop after that many iterations
-    (the loops' own argument, diffusion.py:425)."""
+    (the loops' own argument, diffusion.py:425); `constrained` = round the last latent to the best row the decode path accepts
+    (grammar_util.constrain_tokens with `bars`, on the local shard before the gather) and return (tokens, ConstrainResult), both for
+    the GLOBAL batch."""
     device = model.word_embedding.weight.device
     B = cond["input_ids"].shape[0]
     local = sharding.shard_batch(cond) if sharded else cond
@@ -66,16 +91,17 @@ def generate(model, diffusion, cond, step=None, clip_denoised=True, top_p=1, cla
         lo, hi = sharding.shard_bounds(B) if sharded else (0, B)
         noise = noise[lo:hi].to(device)
     x_noised = torch.where(torch.eq(mask3, 0), x_start, noise)
-    tokens = _run(model, diffusion, x_start, mask3, x_noised, step or diffusion.num_timesteps, t_enc, clip_denoised,
-                  top_p, clamp_step)
-    return sharding.gather_rows(tokens, B) if sharded else tokens
+    out = _run(model, diffusion, x_start, mask3, x_noised, step or diffusion.num_timesteps, t_enc, clip_denoised,
+               top_p, clamp_step, _constrain_args(local, bars, B, sharded) if constrained else None)
+    return _gather(out, B, sharded, constrained)
 
 
 @torch.no_grad()
-def modify(model, diffusion, cond, step, strength=0.75, clip_denoised=True, top_p=1, clamp_step=0, sharded=True, noise=None):
+def modify(model, diffusion, cond, step, strength=0.75, clip_denoised=True, top_p=1, clamp_step=0, sharded=True, noise=None,
+           constrained=False, bars="exact"):
     """Modification mode: q_sample the corrupted sequence to noising_t = int(step * strength), then
     run the reverse loop for noising_t iterations (run/sample.py:195-197, :214).  `noise`: q_sample's draw for the
-    GLOBAL batch, [B, L, E] (default: this rank's device generator, as the reference)."""
+    GLOBAL batch, [B, L, E] (default: this rank's device generator, as the reference).  `constrained`, `bars`: as in `generate`."""
     device = model.word_embedding.weight.device
     B = cond["input_ids"].shape[0]
     local = sharding.shard_batch(cond) if sharded else cond
@@ -86,20 +112,25 @@ def modify(model, diffusion, cond, step, strength=0.75, clip_denoised=True, top_
         lo, hi = sharding.shard_bounds(B) if sharded else (0, B)
         noise = noise[lo:hi].to(device).unsqueeze(-1)
     x_noised = diffusion.q_sample(x_start.unsqueeze(-1), timestep, noise=noise, mask=mask3).squeeze(-1)
-    tokens = _run(model, diffusion, x_start, mask3, x_noised, step, noising_t, clip_denoised, top_p, clamp_step)
-    return sharding.gather_rows(tokens, B) if sharded else tokens
+    out = _run(model, diffusion, x_start, mask3, x_noised, step, noising_t, clip_denoised, top_p, clamp_step,
+               _constrain_args(local, bars, B, sharded) if constrained else None)
+    return _gather(out, B, sharded, constrained)
 
 
 @torch.no_grad()
 def infill(model, diffusion, cond, bars, step=None, strength=1.0, room=0, fields="all", clip_denoised=True, top_p=1, clamp_step=0,
-           sharded=True, noise=None):
+           sharded=True, noise=None, constrained=False):
     """Not in the reference: keep the piece, regenerate bars lo <= k < hi (`bars` = (lo, hi) or an int tensor [B, 2]) - all of their
     notes, with `room` more note slots per bar, or with `fields` ('pitch', ('velocity', 'duration'), ...) only those tokens of their
     notes.  du.plan_infill makes the row and the mask on the GLOBAL batch; the existing paths run under that mask - strength == 1:
     `generate` (noise in the region, all steps), else `modify` (q_sample to int(step * strength)); du.splice_infill brings the gathered
     tokens back: the original tokens outside the region bit for bit, whole notes inside it.  -> (tokens [B, L] int64, du.InfillResult).
     Decode the tokens with cond['input_mask'], not with the plan's mask.  A row that cannot be planned returns unchanged and says why
-    in the result's status."""
+    in the result's status.  constrained=True is refused: the plan's region sits in the middle of the row between tokens that must stay,
+    which the row grammar of grammar_util does not express yet."""
+    if constrained:
+        raise NotImplementedError("infill(constrained=True): the regenerated region lies mid-row between kept tokens; grammar-constrained "
+                                  "rounding needs fixed-token positions for that and covers generate / modify only")
     device = model.word_embedding.weight.device
     plan = du.plan_infill(cond["input_ids"].to(device), cond["input_mask"].to(device), bars, room, fields)
     plan_cond = {"input_ids": plan.tokens, "input_mask": plan.mask}
@@ -116,7 +147,8 @@ def infill(model, diffusion, cond, bars, step=None, strength=1.0, room=0, fields
 class SamplingReport:
     """What a run leaves: total_valid_count (int), totals (evaluation.MetricTotals - a generation run with get_metric:
     evaluation.GenerationTotals - or None), summary (the totals' summary() dict or None), batches (how many the loop ran).  A run with
-    harmony=True adds `harmony` (evaluation.HarmonyTotals.summary(), or None when no batch ran); run_infill adds `infill`."""
+    harmony=True adds `harmony` (evaluation.HarmonyTotals.summary(), or None when no batch ran); run_infill adds `infill`; a run with
+    constrained=True adds `constrained` (gu.ConstrainResult.describe over all batches: rows per status, Bars and notes placed)."""
 
     def __init__(self, total_valid_count, totals, summary, batches):
         self.total_valid_count, self.totals, self.summary, self.batches = total_valid_count, totals, summary, batches
@@ -133,6 +165,15 @@ def _write_rows(mode, rows, batch_index, previous_count, out_dir, log):
             log(out.getvalue())
 
 
+def _constrained_block(d):
+    """the log block of a run with constrained=True"""
+    rows = d["rows"]
+    total = sum(rows.values())
+    kept = ", ".join("%s %d" % (k, v) for k, v in rows.items() if k != "ok" and v)
+    return ("### Grammar-constrained rounding: %d of %d rows rounded to an accepted sequence (%d Bars, %d notes)%s" % (
+        rows["ok"], total, d["bars"], d["notes"], "; left as the plain argmax: " + kept if kept else ""))
+
+
 def _fatal_status(rows):
     """the first status of a DecodedRows on which write_decoded_rows raises, or 0"""
     for st in rows.status:
@@ -143,7 +184,8 @@ def _fatal_status(rows):
 
 @torch.no_grad()
 def run_modification(model, diffusion, data_loader, *, step, strength=0.75, batch_size, out_dir=None, get_metric=True, sampler=None,
-                     clip_denoised=True, top_p=1, clamp_step=0, log=print, harmony=False, harmony_bars=None):
+                     clip_denoised=True, top_p=1, clamp_step=0, log=print, harmony=False, harmony_bars=None, constrained=False,
+                     bars="exact"):
     """run/sample.py:168-317 in modification mode.  data_loader yields {'input_ids', 'input_mask'[, 'correct_ids']} for the GLOBAL
     batch; `sampler(cond)` returns its tokens [B, L] (default: `modify`, sharded when a process group is up).  With get_metric and a
     'correct_ids' in the batch: evaluation.evaluate_batch (strict validation, as the reference when it computes metrics) and the
@@ -153,16 +195,23 @@ def run_modification(model, diffusion, data_loader, *, step, strength=0.75, batc
     then, before the summary, from ONE copy.  Returns a SamplingReport.
     harmony (an addition): the DecodedBatch every batch has anyway also goes through evaluation.HarmonyTotals - one more launch per
     batch, one more device -> host copy after the loop - and the report gains `harmony`, its summary (CH: do the notes fit the chords
-    the piece was conditioned on), logged as evaluation.harmony_block; harmony_bars: HarmonyTotals.update's `bars`."""
+    the piece was conditioned on), logged as evaluation.harmony_block; harmony_bars: HarmonyTotals.update's `bars`.
+    constrained (an addition): the sampler rounds to the best row the decode path accepts (`modify(constrained=True, bars=bars)`; a
+    `sampler` of the caller's then returns (tokens, ConstrainResult) too).  Two more launches per batch, one more device -> host copy
+    after the loop; the report gains `constrained` and _constrained_block is logged.  Without it nothing changes."""
     if sampler is None:
-        sampler = lambda cond: modify(model, diffusion, cond, step, strength, clip_denoised, top_p, clamp_step, sharded=True)  # noqa: E731
+        sampler = lambda cond: modify(model, diffusion, cond, step, strength, clip_denoised, top_p, clamp_step, sharded=True,  # noqa: E731
+                                      **({"constrained": True, "bars": bars} if constrained else {}))
     write = out_dir is not None and sharding.rank() == 0
     if write:
         os.makedirs(out_dir, exist_ok=True)
     totals, total_valid, pending, batches = None, None, [], 0
-    chord_fit = None
+    chord_fit, rounded = None, None
     for batch_index, cond in enumerate(data_loader):
         tokens = sampler(cond)
+        if constrained:
+            tokens, res = tokens
+            rounded = res.vector() if rounded is None else rounded + res.vector()
         dev = tokens.device
         mask = cond["input_mask"].to(dev)
         metric_on = bool(get_metric) and cond.get("correct_ids") is not None
@@ -196,6 +245,8 @@ def run_modification(model, diffusion, data_loader, *, step, strength=0.75, batc
         report = SamplingReport(0, None, None, 0)
         if harmony:
             report.harmony = None
+        if constrained:
+            report.constrained = None
         return report
     # the one copy of a run without out_dir: [total valid | the seven of MetricTotals.vector() | six per pending batch]
     parts = [total_valid.double().reshape(1), totals.vector() if totals is not None else torch.zeros(7, device=total_valid.device, dtype=torch.float64)]
@@ -215,6 +266,9 @@ def run_modification(model, diffusion, data_loader, *, step, strength=0.75, batc
     if harmony:
         report.harmony = chord_fit.summary()
         log(evaluation.harmony_block(report.harmony))
+    if constrained:
+        report.constrained = gu.ConstrainResult.describe(rounded.cpu().tolist())
+        log(_constrained_block(report.constrained))
     return report
 
 
@@ -247,7 +301,7 @@ def run_infill(model, diffusion, data_loader, *, bars, step, strength=1.0, room=
 @torch.no_grad()
 def run_generation(model, diffusion, midi_meta_dict, *, batch_size, seq_len, num_samples, step=None, out_dir, sampler=None,
                    max_batches=None, clip_denoised=True, top_p=1, clamp_step=0, log=print, device="cuda", get_metric=False, corpus=None,
-                   duplicate_threshold=None, harmony=False):
+                   duplicate_threshold=None, harmony=False, constrained=False, bars="exact"):
     """run/sample.py:168-317 in generation mode: ONE meta_to_batch, sampled again and again (infinite_loader_from_single); every batch
     is decoded without strict validation and its valid rows are written as generated_{n:0>7}.midi, n counting on from the running
     total_valid_count (out_dir None: decoded and counted, nothing written).  The loop stops after the batch that reaches num_samples
@@ -258,16 +312,21 @@ def run_generation(model, diffusion, midi_meta_dict, *, batch_size, seq_len, num
     evaluation.GenerationTotals keeps its vectors; after the loop the summary (diversity, duplicates, CP, CV and, with `corpus` =
     [n, 56] get_vectors rows of a training set, novelty and memorised) is logged and fills the report's totals / summary.
     duplicate_threshold: GenerationTotals' (None: its default).  harmony: as in run_modification - the batch's one decode also goes
-    through evaluation.HarmonyTotals and the report gains `harmony`."""
+    through evaluation.HarmonyTotals and the report gains `harmony`.  constrained, bars: as in run_modification, with
+    `generate(constrained=True, bars=bars)` - the report gains `constrained`, from one more copy after the loop."""
     if sampler is None:
-        sampler = lambda cond: generate(model, diffusion, cond, step, clip_denoised, top_p, clamp_step, sharded=True)  # noqa: E731
+        sampler = lambda cond: generate(model, diffusion, cond, step, clip_denoised, top_p, clamp_step, sharded=True,  # noqa: E731
+                                        **({"constrained": True, "bars": bars} if constrained else {}))
     cond = du.meta_to_batch(midi_meta_dict, batch_size, seq_len, device)
     write = out_dir is not None and sharding.rank() == 0
     if write:
         os.makedirs(out_dir, exist_ok=True)
-    total, batch_index, totals, chord_fit = 0, 0, None, None
+    total, batch_index, totals, chord_fit, rounded = 0, 0, None, None, None
     while total < num_samples and (max_batches is None or batch_index < max_batches):
         tokens = sampler(cond)
+        if constrained:
+            tokens, res = tokens
+            rounded = res.vector() if rounded is None else rounded + res.vector()
         mask = cond["input_mask"].to(tokens.device)
         if get_metric:
             if totals is None:
@@ -300,4 +359,8 @@ def run_generation(model, diffusion, midi_meta_dict, *, batch_size, seq_len, num
         report.harmony = chord_fit.summary() if chord_fit is not None else None
         if chord_fit is not None:
             log(evaluation.harmony_block(report.harmony))
+    if constrained:
+        report.constrained = gu.ConstrainResult.describe(rounded.cpu().tolist()) if rounded is not None else None
+        if rounded is not None:
+            log(_constrained_block(report.constrained))
     return report
