@@ -1,7 +1,7 @@
 """ctypes binding of libmusehip.so (C ABI: include/musehip.h, include/musehip_data.h for the dataset loader and
 include/musehip_eval.h for the evaluation of sampled batches, include/musehip_stats.h for the pair statistics of a set,
 include/musehip_infill.h for the infill mask and splice, include/musehip_harmony.h for the chord-fit counts,
-include/musehip_grammar.h for the grammar-constrained rounding).
+include/musehip_grammar.h for the grammar-constrained rounding, include/musehip_region.h for the rounding of infill regions).
 
 There is no fallback: `lib()` raises if the shared library is absent or does not export the
 symbols the header declares.  Build it with `python -c "import __graft_entry__ as g; g.build()"`
@@ -28,6 +28,7 @@ _STATS_H = _abi.load("musehip_stats.h", _H)
 _INFILL_H = _abi.load("musehip_infill.h", _H)
 _HARMONY_H = _abi.load("musehip_harmony.h", _H)
 _GRAMMAR_H = _abi.load("musehip_grammar.h", _H)
+_REGION_H = _abi.load("musehip_region.h", _H)
 
 MH_ERR_INVALID, MH_ERR_HIP, MH_ERR_UNSUPPORTED = (_H.enums["MH_ERR_" + n] for n in ("INVALID", "HIP", "UNSUPPORTED"))
 MH_F32, MH_BF16, MH_BF16X3, MH_F16X3 = (_H.enums["MH_" + n] for n in ("F32", "BF16", "BF16X3", "F16X3"))
@@ -68,6 +69,9 @@ HARMONY_ENUMS = _HARMONY_H.enums
 GRAMMAR_SIGNATURES = _GRAMMAR_H.protos
 GRAMMAR_ENUMS = _GRAMMAR_H.enums
 GrammarClasses = _GRAMMAR_H.structs["mhg_classes"]
+# include/musehip_region.h: the mhr_* entry point (whole-note rounding of an infill plan's regions) and enum mhr_status, exported by both libraries
+REGION_SIGNATURES = _REGION_H.protos
+REGION_ENUMS = _REGION_H.enums
 
 _lib = None
 _handles = {}
@@ -108,7 +112,7 @@ def lib():
     switched to the debug build (use_debug_library / debug_library)."""
     global _lib
     if _lib is None:
-        _lib = _load(LIB_PATH, {**SIGNATURES, **DATA_SIGNATURES, **EVAL_SIGNATURES, **STATS_SIGNATURES, **INFILL_SIGNATURES, **HARMONY_SIGNATURES, **GRAMMAR_SIGNATURES}, "libmusehip.so")
+        _lib = _load(LIB_PATH, {**SIGNATURES, **DATA_SIGNATURES, **EVAL_SIGNATURES, **STATS_SIGNATURES, **INFILL_SIGNATURES, **HARMONY_SIGNATURES, **GRAMMAR_SIGNATURES, **REGION_SIGNATURES}, "libmusehip.so")
     return _lib
 
 
@@ -118,8 +122,8 @@ def use_debug_library(on=True):
     the product never calls this.  Each library has its own switch state; objects made under one (captured graphs, engines' arenas)
     are plain HIP objects and stay valid under the other."""
     global _lib
-    _lib = (_load(DBG_LIB_PATH, {**SIGNATURES, **DATA_SIGNATURES, **EVAL_SIGNATURES, **STATS_SIGNATURES, **INFILL_SIGNATURES, **HARMONY_SIGNATURES, **GRAMMAR_SIGNATURES, **DBG_SIGNATURES}, "libmusehip_dbg.so") if on else
-            _load(LIB_PATH, {**SIGNATURES, **DATA_SIGNATURES, **EVAL_SIGNATURES, **STATS_SIGNATURES, **INFILL_SIGNATURES, **HARMONY_SIGNATURES, **GRAMMAR_SIGNATURES}, "libmusehip.so"))
+    _lib = (_load(DBG_LIB_PATH, {**SIGNATURES, **DATA_SIGNATURES, **EVAL_SIGNATURES, **STATS_SIGNATURES, **INFILL_SIGNATURES, **HARMONY_SIGNATURES, **GRAMMAR_SIGNATURES, **REGION_SIGNATURES, **DBG_SIGNATURES}, "libmusehip_dbg.so") if on else
+            _load(LIB_PATH, {**SIGNATURES, **DATA_SIGNATURES, **EVAL_SIGNATURES, **STATS_SIGNATURES, **INFILL_SIGNATURES, **HARMONY_SIGNATURES, **GRAMMAR_SIGNATURES, **REGION_SIGNATURES}, "libmusehip.so"))
     return _lib
 
 

@@ -236,12 +236,16 @@ class TransformerNetModel(nn.Module):
     def argmax_tokens(self, hidden_repr, constrain=None):
         """argmax(get_logits(x), -1) without materialising the logits (run/sample.py:219-220), in the model's logits_mode.
         constrain (an addition): None, or (input_ids, input_mask[, bars]) of the rows - then the note region of every row is the best
-        sequence the decode path accepts instead (utils/grammar_util.constrain_tokens) and the return is (tokens, ConstrainResult)."""
+        sequence the decode path accepts instead (utils/grammar_util.constrain_tokens) and the return is (tokens, ConstrainResult);
+        or an infill plan (utils/infill_util.InfillPlan) - then the plan's masked slots hold whole notes instead
+        (utils/grammar_util.constrain_region_tokens) and the return is (tokens, RegionResult)."""
         if self.logits_mode not in (1, 2):
             raise NotImplementedError
         if constrain is not None:
-            from ..utils.grammar_util import constrain_tokens
-            return constrain_tokens(self, hidden_repr, *constrain)
+            from ..utils.grammar_util import constrain_region_tokens, constrain_tokens
+            if isinstance(constrain, (tuple, list)):
+                return constrain_tokens(self, hidden_repr, *constrain)
+            return constrain_region_tokens(self, hidden_repr, constrain)
         w, b = self.lm_head.weight.detach(), self.lm_head.bias.detach()
         if self.logits_mode == 2:
             # |W_v|^2: the cache that follows the engine (refreshed with it when any parameter's version changes) while lm_head is tied

@@ -14,11 +14,14 @@ a plan and a splice (utils/infill_util.py, csrc/infill.hip) around `generate` / 
 Nor is `harmony=True` of the three loops: the batch's one decode also goes through evaluation.HarmonyTotals (csrc/harmony.hip) and
 the report says how the notes fit the chords the pieces were conditioned on.  Nor is `constrained=True` of `generate` / `modify` and of the
 loops: the final argmax becomes the best token sequence the decode path accepts (utils/grammar_util.py, csrc/grammar.hip), so that a
-row is not lost to one token in the wrong place; the in-loop clamp (denoised_fn_round) stays as it is."""
+row is not lost to one token in the wrong place; the in-loop clamp (denoised_fn_round) stays as it is.  Nor is `region=` of `generate` /
+`modify` and `rounding="region"` of `infill` / `run_infill`: the slots an infill plan masks are rounded to whole notes and pads
+(gu.constrain_region_tokens, csrc/region.hip), so that the splice drops no token of a broken note."""
 import contextlib
 import io
 import os
 from functools import partial
+from types import SimpleNamespace
 
 import torch
 
@@ -49,7 +52,7 @@ def _run(model, diffusion, x_start, mask3, x_noised, step, noising_t, clip_denoi
                         t_enc=noising_t, only_last=True)                          # sample.py:200-215
     if constrain is None:
         return model.argmax_tokens(samples[-1])                                   # sample.py:218-220
-    return model.argmax_tokens(samples[-1], constrain=constrain)                  # -> (tokens, ConstrainResult)
+    return model.argmax_tokens(samples[-1], constrain=constrain)                  # -> (tokens, ConstrainResult | RegionResult)
 
 
 def _constrain_args(local, bars, B, sharded):
@@ -60,30 +63,55 @@ def _constrain_args(local, bars, B, sharded):
     return local["input_ids"], local["input_mask"], bars
 
 
-def _gather(out, B, sharded, constrained):
-    """the local shard's tokens - with `constrained` (tokens, ConstrainResult), every tensor of it - gathered to the global batch"""
-    if not constrained:
+def _region_args(region, B, sharded):
+    """argmax_tokens' `constrain` for this rank's rows: an infill plan of the GLOBAL batch is cut like the batch"""
+    lo, hi = sharding.shard_bounds(B) if sharded else (0, B)
+    return SimpleNamespace(tokens=region.tokens[lo:hi], mask=region.mask[lo:hi], status=region.status[lo:hi], fields=region.fields)
+
+
+def _rounding(local, B, sharded, constrained, bars, region):
+    """-> (argmax_tokens' `constrain` or None, the class of the result that comes back with the tokens or None)"""
+    if region is not None:
+        if constrained:
+            raise ValueError("region= rounds the slots of an infill plan, constrained=True the whole note region of a row under a Bar "
+                             "budget: one or the other")
+        if tuple(region.tokens.shape) != (B,) + tuple(local["input_ids"].shape[1:]):
+            raise ValueError("region: an infill plan of the GLOBAL batch, whose tokens / mask are cond's input_ids / input_mask")
+        return _region_args(region, B, sharded), gu.RegionResult
+    if constrained:
+        return _constrain_args(local, bars, B, sharded), gu.ConstrainResult
+    return None, None
+
+
+def _gather(out, B, sharded, result):
+    """the local shard's tokens - with a `result` class (tokens, ConstrainResult | RegionResult), every tensor of it - gathered to the
+    global batch"""
+    if result is None:
         return sharding.gather_rows(out, B) if sharded else out
     tokens, res = out
     if sharded:
         tokens = sharding.gather_rows(tokens, B)
-        res = gu.ConstrainResult(*(sharding.gather_rows(t, B) for t in (res.status, res.path_score, res.counts)))
+        res = result(*(sharding.gather_rows(t, B) for t in (res.status, res.path_score, res.counts)))
     return tokens, res
 
 
 @torch.no_grad()
 def generate(model, diffusion, cond, step=None, clip_denoised=True, top_p=1, clamp_step=0, sharded=True, noise=None,
-             t_enc=None, constrained=False, bars="exact"):
+             t_enc=None, constrained=False, bars="exact", region=None):
     """Generation mode: noise everywhere except the anchored meta prefix (run/sample.py:190-193).
     `cond` = {'input_ids', 'input_mask'} for the GLOBAL batch; returns int64 tokens [B, L] on every rank.
     Additions to the reference's block: `noise` = the start latent's draw for the GLOBAL batch (each rank takes its rows;
     default: this rank's `torch.randn_like`, as the reference), `t_enc` = stop after that many iterations
     (the loops' own argument, diffusion.py:425); `constrained` = round the last latent to the best row the decode path accepts
     (grammar_util.constrain_tokens with `bars`, on the local shard before the gather) and return (tokens, ConstrainResult), both for
-    the GLOBAL batch."""
+    the GLOBAL batch; `region` = an infill plan (du.plan_infill) of the GLOBAL batch whose tokens / mask are `cond`'s input_ids /
+    input_mask: round the plan's masked slots to whole notes (grammar_util.constrain_region_tokens on the local shard, the plan cut to
+    this rank's rows like the batch) and return (tokens, RegionResult) for the GLOBAL batch.  `region` together with constrained=True
+    raises ValueError."""
     device = model.word_embedding.weight.device
     B = cond["input_ids"].shape[0]
     local = sharding.shard_batch(cond) if sharded else cond
+    constrain, result = _rounding(local, B, sharded, constrained, bars, region)
     x_start, mask3 = _prepare(model, local, device)
     if noise is None:
         noise = torch.randn_like(x_start)
@@ -92,19 +120,21 @@ def generate(model, diffusion, cond, step=None, clip_denoised=True, top_p=1, cla
         noise = noise[lo:hi].to(device)
     x_noised = torch.where(torch.eq(mask3, 0), x_start, noise)
     out = _run(model, diffusion, x_start, mask3, x_noised, step or diffusion.num_timesteps, t_enc, clip_denoised,
-               top_p, clamp_step, _constrain_args(local, bars, B, sharded) if constrained else None)
-    return _gather(out, B, sharded, constrained)
+               top_p, clamp_step, constrain)
+    return _gather(out, B, sharded, result)
 
 
 @torch.no_grad()
 def modify(model, diffusion, cond, step, strength=0.75, clip_denoised=True, top_p=1, clamp_step=0, sharded=True, noise=None,
-           constrained=False, bars="exact"):
+           constrained=False, bars="exact", region=None):
     """Modification mode: q_sample the corrupted sequence to noising_t = int(step * strength), then
     run the reverse loop for noising_t iterations (run/sample.py:195-197, :214).  `noise`: q_sample's draw for the
-    GLOBAL batch, [B, L, E] (default: this rank's device generator, as the reference).  `constrained`, `bars`: as in `generate`."""
+    GLOBAL batch, [B, L, E] (default: this rank's device generator, as the reference).  `constrained`, `bars`, `region`: as in
+    `generate`."""
     device = model.word_embedding.weight.device
     B = cond["input_ids"].shape[0]
     local = sharding.shard_batch(cond) if sharded else cond
+    constrain, result = _rounding(local, B, sharded, constrained, bars, region)
     x_start, mask3 = _prepare(model, local, device)
     noising_t = int(step * strength)
     timestep = torch.full((x_start.shape[0], 1), noising_t - 1, device=device)
@@ -112,42 +142,50 @@ def modify(model, diffusion, cond, step, strength=0.75, clip_denoised=True, top_
         lo, hi = sharding.shard_bounds(B) if sharded else (0, B)
         noise = noise[lo:hi].to(device).unsqueeze(-1)
     x_noised = diffusion.q_sample(x_start.unsqueeze(-1), timestep, noise=noise, mask=mask3).squeeze(-1)
-    out = _run(model, diffusion, x_start, mask3, x_noised, step, noising_t, clip_denoised, top_p, clamp_step,
-               _constrain_args(local, bars, B, sharded) if constrained else None)
-    return _gather(out, B, sharded, constrained)
+    out = _run(model, diffusion, x_start, mask3, x_noised, step, noising_t, clip_denoised, top_p, clamp_step, constrain)
+    return _gather(out, B, sharded, result)
 
 
 @torch.no_grad()
 def infill(model, diffusion, cond, bars, step=None, strength=1.0, room=0, fields="all", clip_denoised=True, top_p=1, clamp_step=0,
-           sharded=True, noise=None, constrained=False):
+           sharded=True, noise=None, constrained=False, rounding="argmax"):
     """Not in the reference: keep the piece, regenerate bars lo <= k < hi (`bars` = (lo, hi) or an int tensor [B, 2]) - all of their
     notes, with `room` more note slots per bar, or with `fields` ('pitch', ('velocity', 'duration'), ...) only those tokens of their
     notes.  du.plan_infill makes the row and the mask on the GLOBAL batch; the existing paths run under that mask - strength == 1:
     `generate` (noise in the region, all steps), else `modify` (q_sample to int(step * strength)); du.splice_infill brings the gathered
     tokens back: the original tokens outside the region bit for bit, whole notes inside it.  -> (tokens [B, L] int64, du.InfillResult).
     Decode the tokens with cond['input_mask'], not with the plan's mask.  A row that cannot be planned returns unchanged and says why
-    in the result's status.  constrained=True is refused: the plan's region sits in the middle of the row between tokens that must stay,
-    which the row grammar of grammar_util does not express yet."""
+    in the result's status.  rounding: 'argmax' (every region slot by its own argmax; the splice drops every pad, every token of a
+    broken note and every field slot of the wrong class) or 'region' (the same `generate` / `modify` call with region=plan: the region
+    leaves the sampler as whole notes and pads, or per field slot the best token of that field, so the splice drops pads only; the
+    result's `.rounding` is the gu.RegionResult, None for 'argmax').  constrained=True is refused: the plan's region sits in the middle
+    of the row between tokens that must stay, which the row grammar with its Bar budget does not express; rounding='region' is the
+    rounding for an infill."""
     if constrained:
         raise NotImplementedError("infill(constrained=True): the regenerated region lies mid-row between kept tokens; grammar-constrained "
                                   "rounding needs fixed-token positions for that and covers generate / modify only")
+    if rounding not in ("argmax", "region"):
+        raise ValueError("infill: rounding is 'argmax' or 'region', got %r" % (rounding,))
     device = model.word_embedding.weight.device
     plan = du.plan_infill(cond["input_ids"].to(device), cond["input_mask"].to(device), bars, room, fields)
     plan_cond = {"input_ids": plan.tokens, "input_mask": plan.mask}
+    how = {"region": plan} if rounding == "region" else {}
     if strength == 1:
-        raw = generate(model, diffusion, plan_cond, step, clip_denoised, top_p, clamp_step, sharded=sharded, noise=noise)
+        raw = generate(model, diffusion, plan_cond, step, clip_denoised, top_p, clamp_step, sharded=sharded, noise=noise, **how)
     else:
         raw = modify(model, diffusion, plan_cond, step or diffusion.num_timesteps, strength, clip_denoised, top_p, clamp_step,
-                     sharded=sharded, noise=noise)
+                     sharded=sharded, noise=noise, **how)
+    raw, rounded = raw if how else (raw, None)
     tokens, counts = du.splice_infill(plan, raw)
-    return tokens.to(torch.int64), du.InfillResult(plan, counts)
+    return tokens.to(torch.int64), du.InfillResult(plan, counts, rounded)
 
 
 # ------------------------------------------------------------------------------------------------ the loop around the hot block
 class SamplingReport:
     """What a run leaves: total_valid_count (int), totals (evaluation.MetricTotals - a generation run with get_metric:
     evaluation.GenerationTotals - or None), summary (the totals' summary() dict or None), batches (how many the loop ran).  A run with
-    harmony=True adds `harmony` (evaluation.HarmonyTotals.summary(), or None when no batch ran); run_infill adds `infill`; a run with
+    harmony=True adds `harmony` (evaluation.HarmonyTotals.summary(), or None when no batch ran); run_infill adds `infill` and, with
+    rounding='region', `region` (gu.RegionResult.describe over all batches: rows per status, masked slots, notes, pads, segments); a run with
     constrained=True adds `constrained` (gu.ConstrainResult.describe over all batches: rows per status, Bars and notes placed)."""
 
     def __init__(self, total_valid_count, totals, summary, batches):
@@ -274,20 +312,27 @@ def run_modification(model, diffusion, data_loader, *, step, strength=0.75, batc
 
 @torch.no_grad()
 def run_infill(model, diffusion, data_loader, *, bars, step, strength=1.0, room=0, fields="all", batch_size, out_dir=None, get_metric=True,
-               clip_denoised=True, top_p=1, clamp_step=0, log=print, harmony=False):
+               clip_denoised=True, top_p=1, clamp_step=0, log=print, harmony=False, rounding="argmax"):
     """run_modification with `infill` as its sampler: every batch is sampled on its 'correct_ids' where present (the piece itself; its
     'input_ids' are the corrupted copy modification mode starts from), else on 'input_ids', and decoded with the batch's own
     'input_mask'.  Files, numbering, metric blocks and the SamplingReport are that loop's; the report also carries `infill`: the
     InfillResult counts summed over the run (rows per status, kept / pads / other / changed), from one more device -> host copy at
     the end.  harmony: run_modification's, with this run's `bars`: the report's `harmony` also says how the regenerated bars
-    (ch_region) and the kept ones (ch_rest) fit their chords."""
-    acc = []
+    (ch_region) and the kept ones (ch_rest) fit their chords.  rounding: `infill`'s; with 'region' the report gains `region`, the
+    RegionResult counts summed over the run (rows per status, masked slots, notes and pads placed, segments) from one more device ->
+    host copy after the loop, and one more line is logged.  Without it nothing changes: the same launches, copies and log."""
+    if rounding not in ("argmax", "region"):
+        raise ValueError("run_infill: rounding is 'argmax' or 'region', got %r" % (rounding,))
+    how = {"rounding": rounding} if rounding != "argmax" else {}
+    acc, racc = [], []
 
     def sampler(cond):
         ids = cond["correct_ids"] if cond.get("correct_ids") is not None else cond["input_ids"]
         tokens, res = infill(model, diffusion, {"input_ids": ids, "input_mask": cond["input_mask"]}, bars, step, strength, room, fields,
-                             clip_denoised, top_p, clamp_step, sharded=True)
+                             clip_denoised, top_p, clamp_step, sharded=True, **how)
         acc[:] = [res.vector() if not acc else acc[0] + res.vector()]
+        if res.rounding is not None:
+            racc[:] = [res.rounding.vector() if not racc else racc[0] + res.rounding.vector()]
         return tokens
 
     report = run_modification(model, diffusion, data_loader, step=step, strength=strength, batch_size=batch_size, out_dir=out_dir,
@@ -295,6 +340,10 @@ def run_infill(model, diffusion, data_loader, *, bars, step, strength=1.0, room=
     report.infill = du.InfillResult.describe(acc[0].cpu().tolist() if acc else [0] * 9)
     log("### Infill: rows %s, region tokens kept %d, pads dropped %d, other dropped %d, changed %d" % (
         report.infill["rows"], report.infill["kept"], report.infill["pads"], report.infill["other"], report.infill["changed"]))
+    if how:
+        report.region = gu.RegionResult.describe(racc[0].cpu().tolist() if racc else [0] * 9)
+        log("### Region rounding: rows %s, notes placed %d, pads placed %d" % (
+            report.region["rows"], report.region["notes"], report.region["pads"]))
     return report
 
 

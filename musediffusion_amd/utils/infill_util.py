@@ -102,12 +102,13 @@ def splice_infill(plan, sampled):
 
 
 class InfillResult:
-    """What sampling.infill reports beside the tokens: the plan, counts [B, 4] and status [B] (device tensors)."""
+    """What sampling.infill reports beside the tokens: the plan, counts [B, 4] and status [B] (device tensors); rounding: the
+    grammar_util.RegionResult of infill(rounding='region'), else None."""
 
     COUNT_NAMES = ("kept", "pads", "other", "changed")
 
-    def __init__(self, plan, counts):
-        self.plan, self.counts, self.status = plan, counts, plan.status
+    def __init__(self, plan, counts, rounding=None):
+        self.plan, self.counts, self.status, self.rounding = plan, counts, plan.status, rounding
 
     def vector(self):
         """device int64 [9]: rows per status (5), the four counts summed"""
