@@ -341,7 +341,8 @@ int mh_weight_prep(const mh_wprep_item* items, int n_items, int total_tiles, mh_
  * reference's --freeze_embedding, config/train.py:67-68, or one autograd never reached) is skipped by the AdamW arithmetic exactly
  * as torch.optim.AdamW skips `p.grad is None` (train_util.py:95), adds nothing to the norm (:277) and is left alone by the clip,
  * while its EMA copies still take update_ema's step (:21-31 walks every master parameter).  param / grad / moments / EMA
- * pointers must be 16-byte aligned (the host checks). */
+ * pointers must be 16-byte aligned (the host checks), and every chunk's `offset` must be a multiple of 4 elements (the kernels
+ * read 16-byte pieces from `pointer + offset`); `count` is free, the chunks of a table must not overlap. */
 typedef struct mh_opt_tensor {
   float* param; const float* grad; float* exp_avg; float* exp_avg_sq; float* ema[4];
 } mh_opt_tensor;
@@ -362,7 +363,10 @@ int mh_adamw_ema_step(const mh_opt_tensor* tensors, const mh_opt_chunk* chunks, 
 int mh_grad_norm(const mh_opt_tensor* tensors, const mh_opt_chunk* chunks, int n_chunks, float* partial, float* out,
                  mh_stream_t stream);
 /* torch.nn.utils.clip_grad_norm_ on the device (utils/train_util.py:255-264): every gradient *= min(1, max_norm / (norm[0] + 1e-6)),
- * `norm` = the device scalar mh_grad_norm wrote; no host synchronisation */
+ * `norm` = the device scalar mh_grad_norm wrote; no host synchronisation.  The coefficient is formed in fp32; when it is >= 1 no
+ * gradient is written (its bits stay).  As in torch, whose clamp(max=1) keeps a NaN: a NaN norm (one NaN gradient element anywhere)
+ * gives a NaN coefficient and turns every gradient into NaN; an infinite norm gives 0 (0 * inf = NaN where the gradient is inf).
+ * max_norm must be > 0. */
 int mh_clip_grads(const mh_opt_tensor* tensors, const mh_opt_chunk* chunks, int n_chunks, const float* norm, float max_norm,
                   mh_stream_t stream);
 

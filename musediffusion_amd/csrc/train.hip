@@ -674,10 +674,11 @@ __global__ __launch_bounds__(256) void sumsq_chunks_kernel(const mh_opt_tensor* 
   __syncthreads();
   if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
-// torch.nn.utils.clip_grad_norm_: g *= min(1, max_norm / (total_norm + 1e-6)) with the norm read from the device
+// torch.nn.utils.clip_grad_norm_: g *= min(1, max_norm / (total_norm + 1e-6)) with the norm read from the device.  torch's
+// clamp(max=1) keeps a NaN (fminf would return the 1): a NaN norm makes every gradient NaN, as there.  coef >= 1 is false for a NaN.
 __global__ __launch_bounds__(256) void clip_grads_kernel(const mh_opt_tensor* __restrict__ tensors, const mh_opt_chunk* __restrict__ chunks,
                                                         const float* __restrict__ norm, float max_norm) {
-  const float coef = fminf(max_norm / (norm[0] + 1e-6f), 1.0f);
+  const float coef = max_norm / (norm[0] + 1e-6f);
   if (coef >= 1.0f) return;
   const mh_opt_chunk ck = chunks[blockIdx.x];
   if (!tensors[ck.tensor].grad) return;

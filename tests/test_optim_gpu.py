@@ -14,6 +14,15 @@ from musediffusion_amd.optim import FusedAdamWEMA  # noqa: E402
 DEV = "cuda"
 
 
+def norm_rtol(shapes):
+    """the gradient norm's relative bound against float64 for the chunk table FusedAdamWEMA builds over tensors of these shapes
+    (tests/optim_ref.py: the longest chain of fp32 roundings a squared element passes through; a few 1e-6, where 1e-3 stood)"""
+    import optim_ref as orf
+    sizes = [int(np.prod(s)) for s in shapes]
+    gm = orf.gamma(orf.total_depth(orf.Layout("host", sizes, (), orf.split(sizes, 65536))))
+    return gm * (1 + gm) / 2 + orf.U
+
+
 def test_fused_adamw_ema_matches_torch():
     g = torch.Generator().manual_seed(0)
     shapes = [(70000,), (33, 65), (7,), (128, 512)]
@@ -28,8 +37,8 @@ def test_fused_adamw_ema_matches_torch():
         for p, q, gr in zip(cpu_params, dev_params, grads):
             p.grad = gr.clone()
             q.grad = gr.clone().to(DEV)
-        norm_ref = float(torch.sqrt(sum((gr ** 2).sum() for gr in grads)))
-        assert abs(float(opt.grad_norm()) - norm_ref) < 1e-3 * norm_ref
+        norm_ref = float(torch.sqrt(sum((gr.double() ** 2).sum() for gr in grads)))
+        assert abs(float(opt.grad_norm()) - norm_ref) <= norm_rtol(shapes) * norm_ref
         lr = 1e-3 * (1 - step / 10)                       # linear anneal like _anneal_lr (train_util.py:266-272)
         for gp in ref_opt.param_groups:
             gp["lr"] = lr
@@ -131,8 +140,8 @@ def test_parameters_without_a_gradient_are_skipped_like_torch_adamw():
                 assert dev[i].grad.data_ptr() % 16 != 0
             else:
                 dev[i].grad = gr.clone().to(DEV)
-        norm_ref = float(torch.sqrt(sum((cpu[i].grad ** 2).sum() for i in (1, 2))))
-        assert abs(float(opt.clip_grad_norm(0.5)) - norm_ref) < 1e-3 * norm_ref
+        norm_ref = float(torch.sqrt(sum((cpu[i].grad.double() ** 2).sum() for i in (1, 2))))
+        assert abs(float(opt.clip_grad_norm(0.5)) - norm_ref) <= norm_rtol(shapes) * norm_ref
         torch.nn.utils.clip_grad_norm_(cpu, 0.5)
         v_frozen, v_live = dev[0]._version, dev[1]._version
         ref.step()

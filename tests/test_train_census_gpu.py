@@ -6,20 +6,24 @@ that starts taking another path, fails here until a parity case reaches it.
 
 PARITY maps each key to the tests that compare it with a reference: `module::test[id]` for one case, `module::test` for all of a test's
 cases.  The LayerNorm, column-sum, scatter and head-permute entries are generated from the parity matrix' own case lists: each of those
-cases records its launch and asserts the very keys it is listed under here.  The kernels outside the matrix point at older direct
-comparisons, each against a reference and not against another launch of the same kernel: weight_prep_kernel against torch's casts (row-major;
-the panel forms in the matrix), sum_slices_kernel against a matmul of the rounded inputs (and against float64 in the matrix), the optimizer
-kernels against torch.optim.AdamW, the reference's update_ema and torch's clip_grad_norm_ on the CPU."""
+cases records its launch and asserts the very keys it is listed under here.  So are the optimizer step's: one key per number of EMA copies
+(tests/train_census.py: ADAM_KEYS), from the case list of the optimizer matrix (tests/test_optim_matrix_gpu.py), which also holds the norm
+and clip kernels' cases.  Second entries name older direct comparisons, each against a reference and not against another launch of the
+same kernel: weight_prep_kernel against torch's casts (row-major; the panel forms in the matrix), sum_slices_kernel against a matmul of the
+rounded inputs, the optimizer kernels through FusedAdamWEMA against torch.optim.AdamW, the reference's update_ema and torch's
+clip_grad_norm_ on the CPU."""
 import os
 import subprocess
 import sys
 
 import pytest
 
+import test_optim_matrix_gpu as om
 import test_train_matrix_gpu as tm
 import train_census as tc
 
 M = "tests/test_train_matrix_gpu.py::"
+OM = "tests/test_optim_matrix_gpu.py::"
 OPTIM = "tests/test_optim_gpu.py::"
 
 PARITY = {}
@@ -61,12 +65,20 @@ for _k, _t in {
     "repack_panel_kernel": M + "test_repack_panel_each_direction",
     "sum_slices_kernel": M + "test_sum_slices_against_float64",
     "weight_prep_kernel": M + "test_weight_prep_panel_forms",
-    "adamw_ema_kernel": OPTIM + "test_fused_adamw_ema_matches_torch",
-    "sumsq_chunks_kernel": OPTIM + "test_fused_adamw_ema_matches_torch",
-    "sum_partials_kernel": OPTIM + "test_fused_adamw_ema_matches_torch",
-    "clip_grads_kernel": OPTIM + "test_parameters_without_a_gradient_are_skipped_like_torch_adamw",
+    "sumsq_chunks_kernel": OM + "test_grad_norm",
+    "sum_partials_kernel": OM + "test_grad_norm",
+    "clip_grads_kernel": OM + "test_clip_grads",
 }.items():
     _add(_k, _t)
+# the optimizer step: one key per adamw_ema_chunk<NEMA> instantiation, each case of the optimizer matrix under the n_ema it asserts it ran
+assert {_c[2] for _c in om.ADAM_CASES} == set(range(5))
+for _c in om.ADAM_CASES:
+    _add(tc.adam_key(_c[2]), OM + "test_adamw_ema_step[%s]" % om._id(_c))
+# (second entries: the older comparisons with torch.optim.AdamW, update_ema and clip_grad_norm_ through FusedAdamWEMA)
+for _k in (tc.adam_key(3), "sumsq_chunks_kernel", "sum_partials_kernel"):
+    _add(_k, OPTIM + "test_fused_adamw_ema_matches_torch")
+for _k in (tc.adam_key(1), "clip_grads_kernel"):
+    _add(_k, OPTIM + "test_parameters_without_a_gradient_are_skipped_like_torch_adamw")
 _add("sum_slices_kernel", "tests/test_kernels_gpu.py::test_gemm_dw_k_major")
 _add("weight_prep_kernel", "tests/test_kernels_gpu.py::test_weight_prep_one_launch_copies_and_transposes")
 

@@ -1,4 +1,5 @@
-"""Parity matrix of the training kernels (csrc/train.hip): every C entry point called through the library's ABI against a float64 reference
+"""Parity matrix of the training kernels (csrc/train.hip): every C entry point but the optimizer's three (mh_adamw_ema_step, mh_grad_norm,
+mh_clip_grads: tests/test_optim_matrix_gpu.py, by the same rules) called through the library's ABI against a float64 reference
 on the CPU (tests/train_ref.py), EVERY element of EVERY output, at the shapes where a streaming kernel goes wrong - a single lane in the
 last 16-byte chunk column (H = 520, 1032), the four-chunk LayerNorm build (H > 1024), blocks and waves that own no row, the partial
 fold's unrolled loop (more than 48 partials) and its tail, a second pass over the embedding columns (E > 256), the 32-chunk scatter,

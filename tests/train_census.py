@@ -5,7 +5,8 @@
   (`ln_bwd_kernel<bf16, 1, true>`, `colsum8_partial_kernel<float>`); where a kernel's path depends on a runtime argument the text does not
   show, the launch note does and the key takes the class of it that selects the path: the LayerNorm backward's second-output form, the head
   permutes' mode, whether the partial fold's unrolled loop runs (P > 48) and whether it accumulates, the scatter's chunk form and column
-  passes, the squared error's vector or scalar loop.
+  passes, the squared error's vector or scalar loop, the number of EMA copies of the optimizer step (`chunks=%d n_ema=%d`: it selects one of
+  the five adamw_ema_chunk<NEMA> instantiations, `ADAM_KEYS`).
 * `record`: tests/gemm_census.py's recorder for this family -> [(key, note, grid)].
 * `WORKLOADS`: the GEMM census' training runs, the seq_len 128 run again in fp32 (the only place the `float` instantiations are launched),
   and one optimizer step (clip + AdamW / EMA + gradient norm), all eager."""
@@ -38,6 +39,14 @@ def scatter_key(chunks, E):
     return "scatter_rows_partial_kernel | chunks%s32 passes=%d" % ("=" if int(chunks) == 32 else "<", (int(E) + 255) // 256)
 
 
+def adam_key(n_ema):
+    return "adamw_ema_kernel | n_ema=%d" % int(n_ema)
+
+
+# the five instantiations of adamw_ema_chunk<NEMA> the kernel's switch selects from mh_opt_hparams.n_ema
+ADAM_KEYS = tuple(adam_key(k) for k in range(5))
+
+
 def census_key(kernel, note):
     """(kernel text, launch note) -> census key, or None for a kernel outside csrc/train.hip"""
     name = " ".join(kernel.strip().strip("()").split())
@@ -55,6 +64,8 @@ def census_key(kernel, note):
         return scatter_key(kv["chunks"], kv["E"]) if "chunks" in kv else name + " | chunks=? passes=?"
     if base == "sqdiff_mean_kernel":
         return "%s | vec=%s" % (name, kv.get("vec", "?"))
+    if base == "adamw_ema_kernel":
+        return "%s | n_ema=%s" % (name, kv.get("n_ema", "?"))
     return name
 
 
