@@ -69,3 +69,17 @@ __device__ __forceinline__ void step_update4(f32x4& x0, const f32x4& xt, const f
     }
   }
 }
+
+// include/musehip_solver.h (DPM-Solver++(2M), data prediction) on one element: x0 comes in as the (rounded) prediction and goes out
+// clipped; the sample is a x_t + b x0, plus c times the previous step's prediction when the row has a history term (hist: c != 0 and
+// a history buffer - the caller loads `prev` only then).  Anchoring is the caller's.  The one definition of the stand-alone kernels'
+// arithmetic (solver.hip: 4 elements per thread or one), FP contraction off inside it, so both forms produce the same bits.
+__device__ __forceinline__ float solver_update1(float& x0, float xt, float prev, float a, float b, float c, int clip, bool hist) {
+#pragma clang fp contract(off)
+  float v = x0;
+  if (clip) v = fminf(fmaxf(v, -1.0f), 1.0f);
+  x0 = v;
+  float out = a * xt + b * v;
+  if (hist) out = out + c * prev;
+  return out;
+}

@@ -316,6 +316,25 @@ def step_epilogue(kind, model_out, x_t, noise, coef, coef_per_batch, clip, round
     return out, x0, mean
 
 
+def dpmpp_epilogue(model_out, x_t, coef, coef_per_batch, clip, x0_prev=None, round_idx=None, table=None, slots=None, mask=None,
+                   x_start=None, out=None, pred_xstart=None, want_x0=True):
+    """Fused multistep DPM-Solver++ tail (include/musehip_solver.h): out = a x_t + b x0 (+ c x0_prev), anchored where mask == 0.
+    coef: [8] or [B, 8] fp32 rows (a, b, c, 0 ...); x0 from `slots` = (pbest or None, pidx, nslots), else table[round_idx], else
+    model_out; x0_prev may be the tensor given as pred_xstart, out may be x_t.  Returns (sample, pred_xstart)."""
+    x_t = _c(x_t, torch.float32)
+    require_device(x_t, coef)
+    B, E = x_t.shape[0], x_t.shape[-1]
+    m, per_elem = _mask_args(mask, x_t)
+    out = torch.empty_like(x_t) if out is None else out
+    if pred_xstart is None and want_x0:
+        pred_xstart = torch.empty_like(x_t)
+    pbest, pidx, nslots = slots if slots is not None else (None, None, 0)
+    check(lib().mhv_dpmpp_epilogue(ptr(model_out), ptr(x_t), ptr(x0_prev), ptr(round_idx), ptr(pbest), ptr(pidx), int(nslots), ptr(table),
+                                   ptr(coef), int(coef_per_batch), int(bool(clip)), ptr(m), per_elem, ptr(x_start), ptr(out),
+                                   ptr(pred_xstart), B, x_t.numel() // B, E, current_stream()), "mhv_dpmpp_epilogue")
+    return out, pred_xstart
+
+
 def trunc_normal(shape, bound, seed, stream_id=0, step_counter=None, device="cuda", out=None):
     out = torch.empty(shape, device=device, dtype=torch.float32) if out is None else out
     check(lib().mh_trunc_normal(ptr(out), out.numel(), float(bound or 0.0), int(seed) & (2 ** 64 - 1), int(stream_id),

@@ -38,9 +38,24 @@ def _prepare(model, cond, device):
     return x_start, mask3
 
 
-def _run(model, diffusion, x_start, mask3, x_noised, step, noising_t, clip_denoised, top_p, clamp_step, constrain=None):
+def _solver(solver, solver_order):
+    """-> the keyword arguments of _run that say which reverse loop runs ({} for the reference's)"""
+    if solver not in ("ddim", "dpmpp"):
+        raise ValueError("solver is 'ddim' or 'dpmpp', got %r" % (solver,))
+    if solver == "ddim":
+        return {}
+    if solver_order not in (1, 2):
+        raise ValueError("solver_order is 1 or 2, got %r" % (solver_order,))
+    return {"solver": solver, "solver_order": solver_order}
+
+
+def _run(model, diffusion, x_start, mask3, x_noised, step, noising_t, clip_denoised, top_p, clamp_step, constrain=None, solver="ddim",
+         solver_order=2):
     T = diffusion.num_timesteps
-    if step == T:                                                                 # sample.py:109-114
+    if solver == "dpmpp":
+        # not in the reference: multistep DPM-Solver++ for every step count, the ancestral loop's (gap 1) included
+        gap, sample_fn = max(1, T // step), partial(diffusion.dpmpp_sample_loop, order=solver_order)
+    elif step == T:                                                               # sample.py:109-114
         gap, sample_fn = 1, diffusion.p_sample_loop
     else:
         gap, sample_fn = T // step, diffusion.ddim_sample_loop
@@ -97,7 +112,7 @@ def _gather(out, B, sharded, result):
 
 @torch.no_grad()
 def generate(model, diffusion, cond, step=None, clip_denoised=True, top_p=1, clamp_step=0, sharded=True, noise=None,
-             t_enc=None, constrained=False, bars="exact", region=None):
+             t_enc=None, constrained=False, bars="exact", region=None, solver="ddim", solver_order=2):
     """Generation mode: noise everywhere except the anchored meta prefix (run/sample.py:190-193).
     `cond` = {'input_ids', 'input_mask'} for the GLOBAL batch; returns int64 tokens [B, L] on every rank.
     Additions to the reference's block: `noise` = the start latent's draw for the GLOBAL batch (each rank takes its rows;
@@ -107,7 +122,10 @@ def generate(model, diffusion, cond, step=None, clip_denoised=True, top_p=1, cla
     the GLOBAL batch; `region` = an infill plan (du.plan_infill) of the GLOBAL batch whose tokens / mask are `cond`'s input_ids /
     input_mask: round the plan's masked slots to whole notes (grammar_util.constrain_region_tokens on the local shard, the plan cut to
     this rank's rows like the batch) and return (tokens, RegionResult) for the GLOBAL batch.  `region` together with constrained=True
-    raises ValueError."""
+    raises ValueError.  `solver`: "ddim" - the reference's loops, ancestral at step == T and its DDIM otherwise - or "dpmpp": the
+    multistep DPM-Solver++ loop (diffusion.dpmpp_sample_loop, gap = T // step) of order `solver_order` (1 or 2); the roundings after
+    the loop (`constrained`, `region`) are the same."""
+    how = _solver(solver, solver_order)
     device = model.word_embedding.weight.device
     B = cond["input_ids"].shape[0]
     local = sharding.shard_batch(cond) if sharded else cond
@@ -120,17 +138,18 @@ def generate(model, diffusion, cond, step=None, clip_denoised=True, top_p=1, cla
         noise = noise[lo:hi].to(device)
     x_noised = torch.where(torch.eq(mask3, 0), x_start, noise)
     out = _run(model, diffusion, x_start, mask3, x_noised, step or diffusion.num_timesteps, t_enc, clip_denoised,
-               top_p, clamp_step, constrain)
+               top_p, clamp_step, constrain, **how)
     return _gather(out, B, sharded, result)
 
 
 @torch.no_grad()
 def modify(model, diffusion, cond, step, strength=0.75, clip_denoised=True, top_p=1, clamp_step=0, sharded=True, noise=None,
-           constrained=False, bars="exact", region=None):
+           constrained=False, bars="exact", region=None, solver="ddim", solver_order=2):
     """Modification mode: q_sample the corrupted sequence to noising_t = int(step * strength), then
     run the reverse loop for noising_t iterations (run/sample.py:195-197, :214).  `noise`: q_sample's draw for the
     GLOBAL batch, [B, L, E] (default: this rank's device generator, as the reference).  `constrained`, `bars`, `region`: as in
-    `generate`."""
+    `generate`; so are `solver` and `solver_order`."""
+    how = _solver(solver, solver_order)
     device = model.word_embedding.weight.device
     B = cond["input_ids"].shape[0]
     local = sharding.shard_batch(cond) if sharded else cond
@@ -142,13 +161,13 @@ def modify(model, diffusion, cond, step, strength=0.75, clip_denoised=True, top_
         lo, hi = sharding.shard_bounds(B) if sharded else (0, B)
         noise = noise[lo:hi].to(device).unsqueeze(-1)
     x_noised = diffusion.q_sample(x_start.unsqueeze(-1), timestep, noise=noise, mask=mask3).squeeze(-1)
-    out = _run(model, diffusion, x_start, mask3, x_noised, step, noising_t, clip_denoised, top_p, clamp_step, constrain)
+    out = _run(model, diffusion, x_start, mask3, x_noised, step, noising_t, clip_denoised, top_p, clamp_step, constrain, **how)
     return _gather(out, B, sharded, result)
 
 
 @torch.no_grad()
 def infill(model, diffusion, cond, bars, step=None, strength=1.0, room=0, fields="all", clip_denoised=True, top_p=1, clamp_step=0,
-           sharded=True, noise=None, constrained=False, rounding="argmax"):
+           sharded=True, noise=None, constrained=False, rounding="argmax", solver="ddim", solver_order=2):
     """Not in the reference: keep the piece, regenerate bars lo <= k < hi (`bars` = (lo, hi) or an int tensor [B, 2]) - all of their
     notes, with `room` more note slots per bar, or with `fields` ('pitch', ('velocity', 'duration'), ...) only those tokens of their
     notes.  du.plan_infill makes the row and the mask on the GLOBAL batch; the existing paths run under that mask - strength == 1:
@@ -160,21 +179,22 @@ def infill(model, diffusion, cond, bars, step=None, strength=1.0, room=0, fields
     leaves the sampler as whole notes and pads, or per field slot the best token of that field, so the splice drops pads only; the
     result's `.rounding` is the gu.RegionResult, None for 'argmax').  constrained=True is refused: the plan's region sits in the middle
     of the row between tokens that must stay, which the row grammar with its Bar budget does not express; rounding='region' is the
-    rounding for an infill."""
+    rounding for an infill.  solver, solver_order: `generate`'s."""
     if constrained:
         raise NotImplementedError("infill(constrained=True): the regenerated region lies mid-row between kept tokens; grammar-constrained "
                                   "rounding needs fixed-token positions for that and covers generate / modify only")
     if rounding not in ("argmax", "region"):
         raise ValueError("infill: rounding is 'argmax' or 'region', got %r" % (rounding,))
+    loop = _solver(solver, solver_order)
     device = model.word_embedding.weight.device
     plan = du.plan_infill(cond["input_ids"].to(device), cond["input_mask"].to(device), bars, room, fields)
     plan_cond = {"input_ids": plan.tokens, "input_mask": plan.mask}
     how = {"region": plan} if rounding == "region" else {}
     if strength == 1:
-        raw = generate(model, diffusion, plan_cond, step, clip_denoised, top_p, clamp_step, sharded=sharded, noise=noise, **how)
+        raw = generate(model, diffusion, plan_cond, step, clip_denoised, top_p, clamp_step, sharded=sharded, noise=noise, **how, **loop)
     else:
         raw = modify(model, diffusion, plan_cond, step or diffusion.num_timesteps, strength, clip_denoised, top_p, clamp_step,
-                     sharded=sharded, noise=noise, **how)
+                     sharded=sharded, noise=noise, **how, **loop)
     raw, rounded = raw if how else (raw, None)
     tokens, counts = du.splice_infill(plan, raw)
     return tokens.to(torch.int64), du.InfillResult(plan, counts, rounded)
@@ -223,7 +243,7 @@ def _fatal_status(rows):
 @torch.no_grad()
 def run_modification(model, diffusion, data_loader, *, step, strength=0.75, batch_size, out_dir=None, get_metric=True, sampler=None,
                      clip_denoised=True, top_p=1, clamp_step=0, log=print, harmony=False, harmony_bars=None, constrained=False,
-                     bars="exact"):
+                     bars="exact", solver="ddim", solver_order=2):
     """run/sample.py:168-317 in modification mode.  data_loader yields {'input_ids', 'input_mask'[, 'correct_ids']} for the GLOBAL
     batch; `sampler(cond)` returns its tokens [B, L] (default: `modify`, sharded when a process group is up).  With get_metric and a
     'correct_ids' in the batch: evaluation.evaluate_batch (strict validation, as the reference when it computes metrics) and the
@@ -236,10 +256,12 @@ def run_modification(model, diffusion, data_loader, *, step, strength=0.75, batc
     the piece was conditioned on), logged as evaluation.harmony_block; harmony_bars: HarmonyTotals.update's `bars`.
     constrained (an addition): the sampler rounds to the best row the decode path accepts (`modify(constrained=True, bars=bars)`; a
     `sampler` of the caller's then returns (tokens, ConstrainResult) too).  Two more launches per batch, one more device -> host copy
-    after the loop; the report gains `constrained` and _constrained_block is logged.  Without it nothing changes."""
+    after the loop; the report gains `constrained` and _constrained_block is logged.  Without it nothing changes.
+    solver, solver_order (an addition): `modify`'s - which reverse loop the default sampler runs."""
+    loop = _solver(solver, solver_order)
     if sampler is None:
         sampler = lambda cond: modify(model, diffusion, cond, step, strength, clip_denoised, top_p, clamp_step, sharded=True,  # noqa: E731
-                                      **({"constrained": True, "bars": bars} if constrained else {}))
+                                      **({"constrained": True, "bars": bars} if constrained else {}), **loop)
     write = out_dir is not None and sharding.rank() == 0
     if write:
         os.makedirs(out_dir, exist_ok=True)
@@ -312,7 +334,7 @@ def run_modification(model, diffusion, data_loader, *, step, strength=0.75, batc
 
 @torch.no_grad()
 def run_infill(model, diffusion, data_loader, *, bars, step, strength=1.0, room=0, fields="all", batch_size, out_dir=None, get_metric=True,
-               clip_denoised=True, top_p=1, clamp_step=0, log=print, harmony=False, rounding="argmax"):
+               clip_denoised=True, top_p=1, clamp_step=0, log=print, harmony=False, rounding="argmax", solver="ddim", solver_order=2):
     """run_modification with `infill` as its sampler: every batch is sampled on its 'correct_ids' where present (the piece itself; its
     'input_ids' are the corrupted copy modification mode starts from), else on 'input_ids', and decoded with the batch's own
     'input_mask'.  Files, numbering, metric blocks and the SamplingReport are that loop's; the report also carries `infill`: the
@@ -320,10 +342,12 @@ def run_infill(model, diffusion, data_loader, *, bars, step, strength=1.0, room=
     the end.  harmony: run_modification's, with this run's `bars`: the report's `harmony` also says how the regenerated bars
     (ch_region) and the kept ones (ch_rest) fit their chords.  rounding: `infill`'s; with 'region' the report gains `region`, the
     RegionResult counts summed over the run (rows per status, masked slots, notes and pads placed, segments) from one more device ->
-    host copy after the loop, and one more line is logged.  Without it nothing changes: the same launches, copies and log."""
+    host copy after the loop, and one more line is logged.  Without it nothing changes: the same launches, copies and log.
+    solver, solver_order: `infill`'s."""
     if rounding not in ("argmax", "region"):
         raise ValueError("run_infill: rounding is 'argmax' or 'region', got %r" % (rounding,))
     how = {"rounding": rounding} if rounding != "argmax" else {}
+    how.update(_solver(solver, solver_order))
     acc, racc = [], []
 
     def sampler(cond):
@@ -350,7 +374,7 @@ def run_infill(model, diffusion, data_loader, *, bars, step, strength=1.0, room=
 @torch.no_grad()
 def run_generation(model, diffusion, midi_meta_dict, *, batch_size, seq_len, num_samples, step=None, out_dir, sampler=None,
                    max_batches=None, clip_denoised=True, top_p=1, clamp_step=0, log=print, device="cuda", get_metric=False, corpus=None,
-                   duplicate_threshold=None, harmony=False, constrained=False, bars="exact"):
+                   duplicate_threshold=None, harmony=False, constrained=False, bars="exact", solver="ddim", solver_order=2):
     """run/sample.py:168-317 in generation mode: ONE meta_to_batch, sampled again and again (infinite_loader_from_single); every batch
     is decoded without strict validation and its valid rows are written as generated_{n:0>7}.midi, n counting on from the running
     total_valid_count (out_dir None: decoded and counted, nothing written).  The loop stops after the batch that reaches num_samples
@@ -362,10 +386,12 @@ def run_generation(model, diffusion, midi_meta_dict, *, batch_size, seq_len, num
     [n, 56] get_vectors rows of a training set, novelty and memorised) is logged and fills the report's totals / summary.
     duplicate_threshold: GenerationTotals' (None: its default).  harmony: as in run_modification - the batch's one decode also goes
     through evaluation.HarmonyTotals and the report gains `harmony`.  constrained, bars: as in run_modification, with
-    `generate(constrained=True, bars=bars)` - the report gains `constrained`, from one more copy after the loop."""
+    `generate(constrained=True, bars=bars)` - the report gains `constrained`, from one more copy after the loop.
+    solver, solver_order: `generate`'s - which reverse loop the default sampler runs."""
+    loop = _solver(solver, solver_order)
     if sampler is None:
         sampler = lambda cond: generate(model, diffusion, cond, step, clip_denoised, top_p, clamp_step, sharded=True,  # noqa: E731
-                                        **({"constrained": True, "bars": bars} if constrained else {}))
+                                        **({"constrained": True, "bars": bars} if constrained else {}), **loop)
     cond = du.meta_to_batch(midi_meta_dict, batch_size, seq_len, device)
     write = out_dir is not None and sharding.rank() == 0
     if write:
