@@ -9,7 +9,9 @@ Generation mode has no ground truth (the reference reports nothing there): `eval
 what needs none - diversity and duplicates from the pair statistics of the generated set (metric.pair_stats), novelty against a corpus
 (metric.nearest), CP and CV - under the same rules: masks instead of compaction, one copy at the summary.
 `HarmonyTotals`, an addition for every mode, is CH: how the decoded notes fit the chord progression the piece was conditioned on
-(metric.harmony_counts), for the whole piece and, for an infill, inside and outside the regenerated bars."""
+(metric.harmony_counts), for the whole piece and, for an infill, inside and outside the regenerated bars.
+`StructureTotals`, an addition for every mode, says whether the pieces are shaped like music over time (metric.structure_counts): the
+pitch-class entropy of 1-bar and 4-bar windows and the groove similarity of the bars, read as a gap to real data (`structure_gap`)."""
 import math
 
 import torch
@@ -310,6 +312,93 @@ def harmony_block(s):
              ("pitch_class_entropy", "Pitch-class entropy"), ("ch_region", "CH region"), ("ch_rest", "CH rest"))
     lines += [f"{f' {label}: {s[key]:.6f} ': ^60}" for key, label in names if key in s]
     return "\n".join(lines + [("=" * 60) + "\n"])
+
+
+# ------------------------------------------------------------------------------------------ structure of a run (additions)
+class StructureTotals:
+    """How the pieces of a run are shaped over time, as device sums of metric.structure_counts: the pitch-class entropy of 1-bar and
+    4-bar windows (H1, H4 of the MusDr set), the groove similarity of the bars (GS: 1 - the mean share of sixteenth-note slots on which
+    two bars of a piece disagree about an onset), notes, onsets and empty bars per bar, pitch use per piece.  The numbers are read as a
+    gap to the same statistics of real data (structure_gap).  One mhm_structure_counts launch per `update` on the DecodedBatch the loop
+    has anyway; `summary` is the one device -> host copy.  With several ranks every rank holds the gathered tokens and computes the
+    same totals, as MetricTotals documents."""
+    INT_NAMES = ("rows", "rows_with_notes", "notes", "skipped", "bars", "bars_with_notes", "pitch_classes", "distinct_pitches",
+                 "pitch_range", "onsets", "windows_1", "windows_4")
+    FLOAT_NAMES = ("h1_sum", "h4_sum", "gs_sum", "gs_rows")
+    RATIO_NAMES = ("h1", "h4", "gs", "notes_per_bar", "empty_bars", "pitch_classes", "pitch_range", "distinct_pitches", "onsets_per_bar")
+
+    def __init__(self, device="cuda"):
+        self.ints = torch.zeros(len(self.INT_NAMES), device=device, dtype=torch.int64)
+        self.floats = torch.zeros(len(self.FLOAT_NAMES), device=device, dtype=torch.float64)
+
+    def update(self, decoded, valid=None):
+        """decoded: a DecodedBatch; valid: [B] mask (default: the rows that decoded).  No sync with the host."""
+        # large enough for the batch without asking the device: a bar needs a BAR token (the first may come without one)
+        max_bars = min(metric.STRUCTURE_MAX_BARS, decoded.restored.shape[1] + 1)
+        sc = metric.structure_counts(decoded, valid, max_bars)
+        c = sc.counts.long()
+        ok = sc.status == metric.STRUCTURE_OK
+        some = ok & (c[:, 0] > 0)
+        zero = torch.zeros_like(c[:, 0])
+        per_row = torch.stack([ok.long(), some.long(), c[:, 0], c[:, 1], c[:, 2], c[:, 3], c[:, 4], c[:, 5],
+                               torch.where(some, c[:, 7] - c[:, 6], zero), c[:, 8], c[:, 12], c[:, 13]], 1)
+        self.ints += per_row.sum(0)
+        paired = ok & (c[:, 9] > 0)
+        slots = torch.where(paired, c[:, 11] * c[:, 9], torch.ones_like(zero)).double()
+        gs = torch.where(paired, 1.0 - c[:, 10].double() / slots, torch.zeros_like(slots))
+        self.floats += torch.stack([sc.entropy[:, 0].sum(), sc.entropy[:, 1].sum(), gs.sum(), paired.sum().double()])
+        return self
+
+    def vector(self):
+        """float64 [16] on the device: the twelve integer sums in INT_NAMES order (exact below 2^53), then FLOAT_NAMES"""
+        return torch.cat([self.ints.double(), self.floats])
+
+    @staticmethod
+    def ratios(host):
+        """host: vector() as Python numbers -> the summary; a ratio with an empty denominator is NaN"""
+        div = lambda a, b: float(a) / float(b) if b else float("nan")
+        rows, some, notes, skipped, bars, with_notes, pcs, distinct, prange, onsets, w1, w4 = (int(x) for x in host[:12])
+        h1, h4, gs, gs_rows = (float(x) for x in host[12:16])
+        return {"rows": rows, "notes": notes, "skipped": skipped, "bars": bars, "h1": div(h1, w1), "h4": div(h4, w4), "gs": div(gs, gs_rows),
+                "notes_per_bar": div(notes, with_notes), "empty_bars": 1 - div(with_notes, bars), "pitch_classes": div(pcs, some),
+                "pitch_range": div(prange, some), "distinct_pitches": div(distinct, some), "onsets_per_bar": div(onsets, with_notes)}
+
+    def summary(self):
+        """{"rows", "notes", "skipped", "bars", "h1", "h4", "gs", "notes_per_bar", "empty_bars", "pitch_classes", "pitch_range",
+        "distinct_pitches", "onsets_per_bar"}: rows = the rows counted; notes / skipped = the notes that went into the bars / that did
+        not (a pitch outside 0..127, a start before 0 or behind the table); bars = the bars used, empty ones between notes included;
+        h1, h4 = the mean pitch-class entropy in bits of the 1-bar / 4-bar windows that hold a note; gs = the mean over the rows with
+        two bars and more of 1 - diff / (slots per bar * pairs); notes_per_bar, onsets_per_bar over the bars with notes; empty_bars =
+        the share of used bars without a note; pitch_classes, pitch_range (highest - lowest), distinct_pitches = means over the rows
+        with notes.  The one device -> host copy."""
+        return self.ratios(self.vector().cpu().tolist())
+
+
+def structure_gap(a, b):
+    """the absolute differences of the ratio fields of two StructureTotals summaries (generated against real data); NaN where either
+    side is"""
+    return {k: abs(float(a[k]) - float(b[k])) for k in StructureTotals.RATIO_NAMES}
+
+
+def structure_block(s, title="Structure"):
+    """the structure summary of a run (or, without the counts, a structure_gap), in the style of harmony_block"""
+    lines = ["", f"{f' Summary: {title} ':=^60}"]
+    if "rows" in s:
+        rows, notes, bars = s["rows"], s["notes"], s["bars"]
+        lines += [f"{f' Rows: {rows} ': ^60}", f"{f' Notes: {notes} in {bars} bars ': ^60}"]
+    names = (("h1", "H1"), ("h4", "H4"), ("gs", "GS"), ("notes_per_bar", "Notes per bar"), ("onsets_per_bar", "Onsets per bar"),
+             ("empty_bars", "Empty bars"), ("pitch_classes", "Pitch classes"), ("distinct_pitches", "Distinct pitches"),
+             ("pitch_range", "Pitch range"))
+    lines += [f"{f' {label}: {s[key]:.6f} ': ^60}" for key, label in names if key in s]
+    return "\n".join(lines + [("=" * 60) + "\n"])
+
+
+def structure_report(generated, reference=None):
+    """what a loop's report carries as `structure`: {"generated"[, "reference", "gap"]} from two summaries"""
+    out = {"generated": generated}
+    if reference is not None:
+        out.update(reference=reference, gap=structure_gap(generated, reference))
+    return out
 
 
 def generation_block(s):

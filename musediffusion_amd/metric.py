@@ -7,7 +7,9 @@ three similarity matrices come from the library's exact-fp32 MFMA GEMM.
 Additions without a reference counterpart: `nearest` / `ONNC_sets` (the fused 1-NN kernel, csrc/evaluate.hip) and `pair_stats` /
 `diversity` (sum and counts over all pairs of a set, csrc/pairstats.hip); neither writes the similarity matrix.  `harmony_counts` /
 `Controllability_Harmony` (csrc/harmony.hip) are CH, the control metric of the ComMU paper the reference never wrote: do the notes of
-a decoded piece fit the chord progression it was conditioned on.
+a decoded piece fit the chord progression it was conditioned on.  `structure_counts` (csrc/structure.hip) are the per-bar counts
+behind H1 / H4 (pitch-class entropy of 1-bar and 4-bar windows) and GS (groove similarity) of the MusDr set: is a piece shaped like
+music over time.
 
 Where this module differs from the reference, on purpose (pinned by tests/test_batch_matrix_gpu.py):
   * get_vectors never raises: status 1 = no BAR token (the reference: IndexError), 2 = a malformed note group or a row that ends
@@ -17,9 +19,10 @@ Where this module differs from the reference, on purpose (pinned by tests/test_b
     0 / 0 = NaN harmony vector the reference returns for those.
   * Controllability_Pitch judges a range token (meta[3]) outside 630..637 by the nearest range (below 631 as 631, above 637 as
     637) where the reference raises KeyError; a row without pitch tokens counts as wrong, as the reference's NaN mean does."""
+import numpy as np
 import torch
 
-from ._lib import HARMONY_ENUMS, check, current_stream, lib, ptr, require_device
+from ._lib import HARMONY_ENUMS, STRUCTURE_ENUMS, check, current_stream, lib, ptr, require_device
 
 
 def get_vectors(tokens, lengths=None, note_len=128, return_status=False):
@@ -294,3 +297,82 @@ def Controllability_Harmony(decoded, valid=None):
     chord in force at their onset) of the valid rows, as Python ints (total, wrong)."""
     c = harmony_counts(decoded, valid).counts[:, 1:3].sum(0, dtype=torch.int64).cpu().tolist()
     return int(c[0]), int(c[0] - c[1])
+
+
+# ------------------------------------------------------------------------------------------ structure (csrc/structure.hip), additions
+# mirror of enum mhm_status (include/musehip_structure.h)
+STRUCTURE_OK, STRUCTURE_MASKED, STRUCTURE_BAD_META, STRUCTURE_BAD_COUNTS = (STRUCTURE_ENUMS["MHM_" + n] for n in ("OK", "MASKED", "BAD_META", "BAD_COUNTS"))
+STRUCTURE_COUNT_NAMES = ("notes", "skipped", "bars_used", "bars_with_notes", "pitch_classes", "distinct_pitches", "lowest_pitch",
+                         "highest_pitch", "onsets", "pairs", "diff", "slots_per_bar", "windows_1", "windows_4", "reserved_0", "reserved_1")
+STRUCTURE_BAR_NAMES = ("notes", "onset_mask", "lowest_pitch", "highest_pitch") + tuple("pitch_class_%d" % p for p in range(12))
+STRUCTURE_MAX_NOTES, STRUCTURE_MAX_BARS = 32768, 512
+
+_XLOG2X_TABLES = {}
+
+
+def xlog2x_host(n):
+    """numpy float64 [n + 1]: k log2 k, entry 0 = 0 - the table mhm_structure_counts takes its entropies from"""
+    k = np.arange(int(n) + 1, dtype=np.float64)
+    table = np.zeros(int(n) + 1, np.float64)
+    table[1:] = k[1:] * np.log2(k[1:])
+    return table
+
+
+def xlog2x_table(n, device):
+    """xlog2x_host(n) as a float64 tensor on `device`, cached per device and size (uploaded once, not per call)"""
+    key = (int(n), str(device))
+    hit = _XLOG2X_TABLES.get(key)
+    if hit is None:
+        if len(_XLOG2X_TABLES) > 64:
+            _XLOG2X_TABLES.clear()
+        hit = _XLOG2X_TABLES[key] = torch.from_numpy(xlog2x_host(n)).to(device)
+    return hit
+
+
+class StructureCounts:
+    """Device results of one batch (include/musehip_structure.h): counts int32 [B, 16] in STRUCTURE_COUNT_NAMES order, entropy float64
+    [B, 2] = (sum of the pitch-class entropy over the 1-bar windows, over the 4-bar windows; divide by counts[:, 12:14]), status int32
+    [B] (STRUCTURE_OK ...; a row that is not OK has zeros everywhere), bars int32 [B, max_bars, 16] in STRUCTURE_BAR_NAMES order, or
+    None."""
+
+    def __init__(self, counts, entropy, status, bars):
+        self.counts, self.entropy, self.status, self.bars = counts, entropy, status, bars
+
+
+def structure_counts_raw(notes, counts3, meta, valid=None, max_bars=64, return_bars=False):
+    """mhm_structure_counts on the tensors a decode leaves: notes [B, max_notes, 4] = (start tick, end tick, pitch, velocity), counts3
+    [B, 3] = (notes, -, -), meta [B, 11], valid [B] or None (every row) -> StructureCounts.  Per bar of a sixteenth-note grid: notes,
+    pitch-class histogram, onset mask, pitch range; per row the entropy sums of the 1-bar and 4-bar windows and the pairwise distance
+    of the bars' onset masks: the rule is the header's.  Notes that start at or behind bar max_bars are skipped (counts[:, 1]).  ONE
+    launch whatever the batch; nothing syncs with the host."""
+    max_bars = int(max_bars)
+    if notes.dim() != 3 or notes.shape[2] != 4:
+        raise ValueError("structure_counts: notes [B, max_notes, 4]")
+    B, max_notes = notes.shape[0], notes.shape[1]
+    if tuple(counts3.shape) != (B, 3) or tuple(meta.shape) != (B, 11):
+        raise ValueError("structure_counts: counts [B, 3] and meta [B, 11]")
+    if not (1 <= max_notes <= STRUCTURE_MAX_NOTES and 1 <= max_bars <= STRUCTURE_MAX_BARS):
+        raise ValueError("structure_counts: max_notes in 1..%d, max_bars in 1..%d (got %d, %d)" % (
+            STRUCTURE_MAX_NOTES, STRUCTURE_MAX_BARS, max_notes, max_bars))
+    if B < 1:
+        raise ValueError("structure_counts: an empty batch")
+    require_device(notes, counts3, meta, valid)
+    dev = notes.device
+    notes, counts3, meta = (t.to(torch.int32).contiguous() for t in (notes, counts3, meta))
+    valid = _mask_i32(valid, B, dev)
+    table = xlog2x_table(max_notes, dev)
+    counts = torch.empty(B, 16, device=dev, dtype=torch.int32)
+    entropy = torch.empty(B, 2, device=dev, dtype=torch.float64)
+    status = torch.empty(B, device=dev, dtype=torch.int32)
+    bars = torch.empty(B, max_bars, 16, device=dev, dtype=torch.int32) if return_bars else None
+    check(lib().mhm_structure_counts(ptr(notes), ptr(counts3), ptr(meta), ptr(valid), ptr(table), ptr(counts), ptr(entropy), ptr(bars),
+                                     ptr(status), B, max_notes, max_bars, current_stream()), "mhm_structure_counts")
+    return StructureCounts(counts, entropy, status, bars)
+
+
+def structure_counts(decoded, valid=None, max_bars=64, return_bars=False):
+    """structure_counts_raw on a DecodedBatch (utils.decode_util.decode_tokens); valid defaults to the rows that decoded
+    (decoded.status == OK: the lists of the others hold nothing)."""
+    if valid is None:
+        valid = decoded.status == 0
+    return structure_counts_raw(decoded.notes, decoded.counts, decoded.meta, valid, max_bars, return_bars)

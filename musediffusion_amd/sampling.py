@@ -16,7 +16,10 @@ the report says how the notes fit the chords the pieces were conditioned on.  No
 loops: the final argmax becomes the best token sequence the decode path accepts (utils/grammar_util.py, csrc/grammar.hip), so that a
 row is not lost to one token in the wrong place; the in-loop clamp (denoised_fn_round) stays as it is.  Nor is `region=` of `generate` /
 `modify` and `rounding="region"` of `infill` / `run_infill`: the slots an infill plan masks are rounded to whole notes and pads
-(gu.constrain_region_tokens, csrc/region.hip), so that the splice drops no token of a broken note."""
+(gu.constrain_region_tokens, csrc/region.hip), so that the splice drops no token of a broken note.  Nor is `structure=True` of the
+three loops: the batch's one decode also goes through evaluation.StructureTotals (csrc/structure.hip) and the report says how the
+pieces are shaped over time - pitch-class entropy of 1-bar and 4-bar windows, groove similarity of the bars - next to the same
+numbers of the ground truth (modification, infill) or of a summary the caller made from a training set (generation)."""
 import contextlib
 import io
 import os
@@ -206,7 +209,9 @@ class SamplingReport:
     evaluation.GenerationTotals - or None), summary (the totals' summary() dict or None), batches (how many the loop ran).  A run with
     harmony=True adds `harmony` (evaluation.HarmonyTotals.summary(), or None when no batch ran); run_infill adds `infill` and, with
     rounding='region', `region` (gu.RegionResult.describe over all batches: rows per status, masked slots, notes, pads, segments); a run with
-    constrained=True adds `constrained` (gu.ConstrainResult.describe over all batches: rows per status, Bars and notes placed)."""
+    constrained=True adds `constrained` (gu.ConstrainResult.describe over all batches: rows per status, Bars and notes placed); a run with
+    structure=True adds `structure` ({"generated"[, "reference", "gap"]}: evaluation.StructureTotals summaries and their
+    evaluation.structure_gap, or None when no batch ran)."""
 
     def __init__(self, total_valid_count, totals, summary, batches):
         self.total_valid_count, self.totals, self.summary, self.batches = total_valid_count, totals, summary, batches
@@ -232,6 +237,20 @@ def _constrained_block(d):
         rows["ok"], total, d["bars"], d["notes"], "; left as the plain argmax: " + kept if kept else ""))
 
 
+def _structure_report(generated, reference, given, log):
+    """a loop's `structure`: the summaries of its StructureTotals (`reference`: the ground truth's, or None) from ONE device -> host
+    copy, or `given` (a summary made beforehand) as the reference; logged as evaluation.structure_block"""
+    n = len(evaluation.StructureTotals.INT_NAMES) + len(evaluation.StructureTotals.FLOAT_NAMES)
+    host = torch.cat([generated.vector()] + ([reference.vector()] if reference is not None else [])).cpu().tolist()
+    ref = evaluation.StructureTotals.ratios(host[n:]) if reference is not None else given
+    out = evaluation.structure_report(evaluation.StructureTotals.ratios(host[:n]), ref)
+    log(evaluation.structure_block(out["generated"]))
+    if ref is not None:
+        log(evaluation.structure_block(out["reference"], "Structure of the reference"))
+        log(evaluation.structure_block(out["gap"], "Structure gap"))
+    return out
+
+
 def _fatal_status(rows):
     """the first status of a DecodedRows on which write_decoded_rows raises, or 0"""
     for st in rows.status:
@@ -243,7 +262,7 @@ def _fatal_status(rows):
 @torch.no_grad()
 def run_modification(model, diffusion, data_loader, *, step, strength=0.75, batch_size, out_dir=None, get_metric=True, sampler=None,
                      clip_denoised=True, top_p=1, clamp_step=0, log=print, harmony=False, harmony_bars=None, constrained=False,
-                     bars="exact", solver="ddim", solver_order=2):
+                     bars="exact", solver="ddim", solver_order=2, structure=False):
     """run/sample.py:168-317 in modification mode.  data_loader yields {'input_ids', 'input_mask'[, 'correct_ids']} for the GLOBAL
     batch; `sampler(cond)` returns its tokens [B, L] (default: `modify`, sharded when a process group is up).  With get_metric and a
     'correct_ids' in the batch: evaluation.evaluate_batch (strict validation, as the reference when it computes metrics) and the
@@ -257,7 +276,11 @@ def run_modification(model, diffusion, data_loader, *, step, strength=0.75, batc
     constrained (an addition): the sampler rounds to the best row the decode path accepts (`modify(constrained=True, bars=bars)`; a
     `sampler` of the caller's then returns (tokens, ConstrainResult) too).  Two more launches per batch, one more device -> host copy
     after the loop; the report gains `constrained` and _constrained_block is logged.  Without it nothing changes.
-    solver, solver_order (an addition): `modify`'s - which reverse loop the default sampler runs."""
+    solver, solver_order (an addition): `modify`'s - which reverse loop the default sampler runs.
+    structure (an addition): the batch's DecodedBatch also goes through evaluation.StructureTotals - one more launch per batch - and,
+    when the batch has 'correct_ids', the ground truth is decoded too (one more decode per batch, validated as the sample is) into a
+    second StructureTotals; one more device -> host copy after the loop for both.  The report gains `structure` = {"generated",
+    "reference", "gap"} (without ground truth: "generated" only), logged as evaluation.structure_block.  Without it nothing changes."""
     loop = _solver(solver, solver_order)
     if sampler is None:
         sampler = lambda cond: modify(model, diffusion, cond, step, strength, clip_denoised, top_p, clamp_step, sharded=True,  # noqa: E731
@@ -266,7 +289,7 @@ def run_modification(model, diffusion, data_loader, *, step, strength=0.75, batc
     if write:
         os.makedirs(out_dir, exist_ok=True)
     totals, total_valid, pending, batches = None, None, [], 0
-    chord_fit, rounded = None, None
+    chord_fit, rounded, shape, shape_ref = None, None, None, None
     for batch_index, cond in enumerate(data_loader):
         tokens = sampler(cond)
         if constrained:
@@ -288,6 +311,11 @@ def run_modification(model, diffusion, data_loader, *, step, strength=0.75, batc
         total_valid = count.clone() if total_valid is None else total_valid + count
         if harmony:
             chord_fit = (chord_fit or evaluation.HarmonyTotals(dev)).update(dec, bars=harmony_bars)
+        if structure:
+            shape = (shape or evaluation.StructureTotals(dev)).update(dec)
+            if cond.get("correct_ids") is not None:
+                truth = du.decode_tokens(cond["correct_ids"].to(dev), mask, strict_validation=metric_on)
+                shape_ref = (shape_ref or evaluation.StructureTotals(dev)).update(truth)
         if out_dir is not None:
             rows = dec.cpu()
             if write:
@@ -307,6 +335,8 @@ def run_modification(model, diffusion, data_loader, *, step, strength=0.75, batc
             report.harmony = None
         if constrained:
             report.constrained = None
+        if structure:
+            report.structure = None
         return report
     # the one copy of a run without out_dir: [total valid | the seven of MetricTotals.vector() | six per pending batch]
     parts = [total_valid.double().reshape(1), totals.vector() if totals is not None else torch.zeros(7, device=total_valid.device, dtype=torch.float64)]
@@ -329,12 +359,15 @@ def run_modification(model, diffusion, data_loader, *, step, strength=0.75, batc
     if constrained:
         report.constrained = gu.ConstrainResult.describe(rounded.cpu().tolist())
         log(_constrained_block(report.constrained))
+    if structure:
+        report.structure = _structure_report(shape, shape_ref, None, log)
     return report
 
 
 @torch.no_grad()
 def run_infill(model, diffusion, data_loader, *, bars, step, strength=1.0, room=0, fields="all", batch_size, out_dir=None, get_metric=True,
-               clip_denoised=True, top_p=1, clamp_step=0, log=print, harmony=False, rounding="argmax", solver="ddim", solver_order=2):
+               clip_denoised=True, top_p=1, clamp_step=0, log=print, harmony=False, rounding="argmax", solver="ddim", solver_order=2,
+               structure=False):
     """run_modification with `infill` as its sampler: every batch is sampled on its 'correct_ids' where present (the piece itself; its
     'input_ids' are the corrupted copy modification mode starts from), else on 'input_ids', and decoded with the batch's own
     'input_mask'.  Files, numbering, metric blocks and the SamplingReport are that loop's; the report also carries `infill`: the
@@ -343,7 +376,7 @@ def run_infill(model, diffusion, data_loader, *, bars, step, strength=1.0, room=
     (ch_region) and the kept ones (ch_rest) fit their chords.  rounding: `infill`'s; with 'region' the report gains `region`, the
     RegionResult counts summed over the run (rows per status, masked slots, notes and pads placed, segments) from one more device ->
     host copy after the loop, and one more line is logged.  Without it nothing changes: the same launches, copies and log.
-    solver, solver_order: `infill`'s."""
+    solver, solver_order: `infill`'s.  structure: run_modification's - with 'correct_ids' the reference is the piece itself."""
     if rounding not in ("argmax", "region"):
         raise ValueError("run_infill: rounding is 'argmax' or 'region', got %r" % (rounding,))
     how = {"rounding": rounding} if rounding != "argmax" else {}
@@ -360,7 +393,8 @@ def run_infill(model, diffusion, data_loader, *, bars, step, strength=1.0, room=
         return tokens
 
     report = run_modification(model, diffusion, data_loader, step=step, strength=strength, batch_size=batch_size, out_dir=out_dir,
-                              get_metric=get_metric, sampler=sampler, log=log, harmony=harmony, harmony_bars=bars if harmony else None)
+                              get_metric=get_metric, sampler=sampler, log=log, harmony=harmony, harmony_bars=bars if harmony else None,
+                              **({"structure": True} if structure else {}))
     report.infill = du.InfillResult.describe(acc[0].cpu().tolist() if acc else [0] * 9)
     log("### Infill: rows %s, region tokens kept %d, pads dropped %d, other dropped %d, changed %d" % (
         report.infill["rows"], report.infill["kept"], report.infill["pads"], report.infill["other"], report.infill["changed"]))
@@ -374,7 +408,8 @@ def run_infill(model, diffusion, data_loader, *, bars, step, strength=1.0, room=
 @torch.no_grad()
 def run_generation(model, diffusion, midi_meta_dict, *, batch_size, seq_len, num_samples, step=None, out_dir, sampler=None,
                    max_batches=None, clip_denoised=True, top_p=1, clamp_step=0, log=print, device="cuda", get_metric=False, corpus=None,
-                   duplicate_threshold=None, harmony=False, constrained=False, bars="exact", solver="ddim", solver_order=2):
+                   duplicate_threshold=None, harmony=False, constrained=False, bars="exact", solver="ddim", solver_order=2,
+                   structure=False, structure_reference=None):
     """run/sample.py:168-317 in generation mode: ONE meta_to_batch, sampled again and again (infinite_loader_from_single); every batch
     is decoded without strict validation and its valid rows are written as generated_{n:0>7}.midi, n counting on from the running
     total_valid_count (out_dir None: decoded and counted, nothing written).  The loop stops after the batch that reaches num_samples
@@ -387,7 +422,11 @@ def run_generation(model, diffusion, midi_meta_dict, *, batch_size, seq_len, num
     duplicate_threshold: GenerationTotals' (None: its default).  harmony: as in run_modification - the batch's one decode also goes
     through evaluation.HarmonyTotals and the report gains `harmony`.  constrained, bars: as in run_modification, with
     `generate(constrained=True, bars=bars)` - the report gains `constrained`, from one more copy after the loop.
-    solver, solver_order: `generate`'s - which reverse loop the default sampler runs."""
+    solver, solver_order: `generate`'s - which reverse loop the default sampler runs.
+    structure: as in run_modification - the batch's one decode also goes through evaluation.StructureTotals (one more launch per
+    batch, one more copy after the loop) and the report gains `structure` = {"generated"}; structure_reference: a
+    StructureTotals.summary() dict made beforehand from a training set - the report then also carries it as "reference" and the
+    "gap" to it."""
     loop = _solver(solver, solver_order)
     if sampler is None:
         sampler = lambda cond: generate(model, diffusion, cond, step, clip_denoised, top_p, clamp_step, sharded=True,  # noqa: E731
@@ -396,7 +435,7 @@ def run_generation(model, diffusion, midi_meta_dict, *, batch_size, seq_len, num
     write = out_dir is not None and sharding.rank() == 0
     if write:
         os.makedirs(out_dir, exist_ok=True)
-    total, batch_index, totals, chord_fit, rounded = 0, 0, None, None, None
+    total, batch_index, totals, chord_fit, rounded, shape = 0, 0, None, None, None, None
     while total < num_samples and (max_batches is None or batch_index < max_batches):
         tokens = sampler(cond)
         if constrained:
@@ -415,6 +454,8 @@ def run_generation(model, diffusion, midi_meta_dict, *, batch_size, seq_len, num
             dec = du.decode_tokens(tokens, mask, strict_validation=False)
         if harmony:
             chord_fit = (chord_fit or evaluation.HarmonyTotals(tokens.device)).update(dec)
+        if structure:
+            shape = (shape or evaluation.StructureTotals(tokens.device)).update(dec)
         rows = dec.cpu()
         if write:
             valid_count, _ = _write_rows("generation", rows, batch_index, total, out_dir, log)
@@ -438,4 +479,6 @@ def run_generation(model, diffusion, midi_meta_dict, *, batch_size, seq_len, num
         report.constrained = gu.ConstrainResult.describe(rounded.cpu().tolist()) if rounded is not None else None
         if rounded is not None:
             log(_constrained_block(report.constrained))
+    if structure:
+        report.structure = _structure_report(shape, None, structure_reference, log) if shape is not None else None
     return report
