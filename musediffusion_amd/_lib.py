@@ -2,7 +2,8 @@
 include/musehip_eval.h for the evaluation of sampled batches, include/musehip_stats.h for the pair statistics of a set,
 include/musehip_infill.h for the infill mask and splice, include/musehip_harmony.h for the chord-fit counts,
 include/musehip_grammar.h for the grammar-constrained rounding, include/musehip_region.h for the rounding of infill regions,
-include/musehip_solver.h for the multistep DPM-Solver++ reverse step, include/musehip_structure.h for the structure counts).
+include/musehip_solver.h for the multistep DPM-Solver++ reverse step, include/musehip_structure.h for the structure counts,
+include/musehip_arrange.h for the interplay counts of the tracks of a song).
 
 There is no fallback: `lib()` raises if the shared library is absent or does not export the
 symbols the header declares.  Build it with `python -c "import __graft_entry__ as g; g.build()"`
@@ -32,6 +33,7 @@ _GRAMMAR_H = _abi.load("musehip_grammar.h", _H)
 _REGION_H = _abi.load("musehip_region.h", _H)
 _SOLVER_H = _abi.load("musehip_solver.h", _H)
 _STRUCTURE_H = _abi.load("musehip_structure.h", _H)
+_ARRANGE_H = _abi.load("musehip_arrange.h", _H)
 
 MH_ERR_INVALID, MH_ERR_HIP, MH_ERR_UNSUPPORTED = (_H.enums["MH_ERR_" + n] for n in ("INVALID", "HIP", "UNSUPPORTED"))
 MH_F32, MH_BF16, MH_BF16X3, MH_F16X3 = (_H.enums["MH_" + n] for n in ("F32", "BF16", "BF16X3", "F16X3"))
@@ -81,6 +83,9 @@ SolverCoef = _SOLVER_H.structs["mhv_solver_coef"]
 # include/musehip_structure.h: the mhm_* entry point (per-bar pitch-class entropy and groove counts of decoded rows) and enum mhm_status, exported by both libraries
 STRUCTURE_SIGNATURES = _STRUCTURE_H.protos
 STRUCTURE_ENUMS = _STRUCTURE_H.enums
+# include/musehip_arrange.h: the mha_* entry points (interplay counts of the rows of a song, the tile they are staged in) and enum mha_status, exported by both libraries
+ARRANGE_SIGNATURES = _ARRANGE_H.protos
+ARRANGE_ENUMS = _ARRANGE_H.enums
 
 _lib = None
 _handles = {}
@@ -121,7 +126,7 @@ def lib():
     switched to the debug build (use_debug_library / debug_library)."""
     global _lib
     if _lib is None:
-        _lib = _load(LIB_PATH, {**SIGNATURES, **DATA_SIGNATURES, **EVAL_SIGNATURES, **STATS_SIGNATURES, **INFILL_SIGNATURES, **HARMONY_SIGNATURES, **GRAMMAR_SIGNATURES, **REGION_SIGNATURES, **SOLVER_SIGNATURES, **STRUCTURE_SIGNATURES}, "libmusehip.so")
+        _lib = _load(LIB_PATH, {**SIGNATURES, **DATA_SIGNATURES, **EVAL_SIGNATURES, **STATS_SIGNATURES, **INFILL_SIGNATURES, **HARMONY_SIGNATURES, **GRAMMAR_SIGNATURES, **REGION_SIGNATURES, **SOLVER_SIGNATURES, **STRUCTURE_SIGNATURES, **ARRANGE_SIGNATURES}, "libmusehip.so")
     return _lib
 
 
@@ -131,8 +136,8 @@ def use_debug_library(on=True):
     the product never calls this.  Each library has its own switch state; objects made under one (captured graphs, engines' arenas)
     are plain HIP objects and stay valid under the other."""
     global _lib
-    _lib = (_load(DBG_LIB_PATH, {**SIGNATURES, **DATA_SIGNATURES, **EVAL_SIGNATURES, **STATS_SIGNATURES, **INFILL_SIGNATURES, **HARMONY_SIGNATURES, **GRAMMAR_SIGNATURES, **REGION_SIGNATURES, **SOLVER_SIGNATURES, **STRUCTURE_SIGNATURES, **DBG_SIGNATURES}, "libmusehip_dbg.so") if on else
-            _load(LIB_PATH, {**SIGNATURES, **DATA_SIGNATURES, **EVAL_SIGNATURES, **STATS_SIGNATURES, **INFILL_SIGNATURES, **HARMONY_SIGNATURES, **GRAMMAR_SIGNATURES, **REGION_SIGNATURES, **SOLVER_SIGNATURES, **STRUCTURE_SIGNATURES}, "libmusehip.so"))
+    _lib = (_load(DBG_LIB_PATH, {**SIGNATURES, **DATA_SIGNATURES, **EVAL_SIGNATURES, **STATS_SIGNATURES, **INFILL_SIGNATURES, **HARMONY_SIGNATURES, **GRAMMAR_SIGNATURES, **REGION_SIGNATURES, **SOLVER_SIGNATURES, **STRUCTURE_SIGNATURES, **ARRANGE_SIGNATURES, **DBG_SIGNATURES}, "libmusehip_dbg.so") if on else
+            _load(LIB_PATH, {**SIGNATURES, **DATA_SIGNATURES, **EVAL_SIGNATURES, **STATS_SIGNATURES, **INFILL_SIGNATURES, **HARMONY_SIGNATURES, **GRAMMAR_SIGNATURES, **REGION_SIGNATURES, **SOLVER_SIGNATURES, **STRUCTURE_SIGNATURES, **ARRANGE_SIGNATURES}, "libmusehip.so"))
     return _lib
 
 

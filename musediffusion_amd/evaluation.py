@@ -11,7 +11,9 @@ what needs none - diversity and duplicates from the pair statistics of the gener
 `HarmonyTotals`, an addition for every mode, is CH: how the decoded notes fit the chord progression the piece was conditioned on
 (metric.harmony_counts), for the whole piece and, for an infill, inside and outside the regenerated bars.
 `StructureTotals`, an addition for every mode, says whether the pieces are shaped like music over time (metric.structure_counts): the
-pitch-class entropy of 1-bar and 4-bar windows and the groove similarity of the bars, read as a gap to real data (`structure_gap`)."""
+pitch-class entropy of 1-bar and 4-bar windows and the groove similarity of the bars, read as a gap to real data (`structure_gap`).
+`InterplayTotals`, an addition for runs whose rows are the tracks of songs (sampling.run_arrangement), says how the tracks of a song
+fit each other (metric.interplay_counts): which intervals sound between them and for how long, and whether the bass lies below."""
 import math
 
 import torch
@@ -215,16 +217,7 @@ class GenerationTotals:
 
 
 # ------------------------------------------------------------------------------------------ chord fit of a run (additions)
-def _first_bar_shift(decoded):
-    """int64 [B]: 1 where the first token of the restored row that the decoder keeps (2..559) is not BAR, else 0.  The decoder counts a
-    BAR only behind the row's first kept token, so in such a row the notes in front of the first BAR fill bar 0 and the bar that BAR
-    opens is bar 1, while an infill plan numbers the bars from the first BAR (bar 0) and gives the tokens before it to no bar:
-    a note's start / ticks_per_bar is its infill ordinal plus this shift."""
-    r = decoded.restored
-    idx = torch.arange(r.shape[1], device=r.device).unsqueeze(0)
-    kept = (r >= 2) & (r <= 559) & (idx < decoded.lengths.unsqueeze(1))
-    first = torch.where(kept.any(1), r.gather(1, kept.int().argmax(1, keepdim=True)).squeeze(1), torch.full_like(r[:, 0], 2))
-    return (first != 2).long()
+_first_bar_shift = du.first_bar_shift                    # shared with utils.arrange_util.align_shift
 
 
 class HarmonyTotals:
@@ -399,6 +392,84 @@ def structure_report(generated, reference=None):
     if reference is not None:
         out.update(reference=reference, gap=structure_gap(generated, reference))
     return out
+
+
+# ------------------------------------------------------------------------------------------ interplay of a run (additions)
+class InterplayTotals:
+    """How the tracks of the songs of a run fit each other, as device int64 sums of metric.interplay_counts: per interval class and
+    per "this row is below / above" the ticks and the pairs of notes that sound together between a row and the other rows of its
+    song, once over all rows and once per track role (meta[9]: tokens 719..725 -> rows 0..6 = unknown, main melody, sub melody,
+    accompaniment, bass, pad, riff; anything else -> row 7), the rows counted, their notes, the accompanied ones and the songs seen.
+    One mha_interplay_counts launch per `update` on the DecodedBatch the loop has anyway; `summary` is the one device -> host copy."""
+    ROLES = 8
+    BASS_ROW, MELODY_ROW = 4, 1
+    SCALAR_NAMES = ("rows", "notes", "accompanied", "songs")
+    RATIO_NAMES = ("dissonance", "unison", "accompanied", "bass_above", "melody_below")
+
+    def __init__(self, device="cuda"):
+        self.ticks = torch.zeros(9, device=device, dtype=torch.int64)
+        self.pairs = torch.zeros(9, device=device, dtype=torch.int64)
+        self.role_ticks = torch.zeros(self.ROLES, 9, device=device, dtype=torch.int64)
+        self.role_pairs = torch.zeros(self.ROLES, 9, device=device, dtype=torch.int64)
+        self.scalars = torch.zeros(len(self.SCALAR_NAMES), device=device, dtype=torch.int64)
+
+    def update(self, decoded, song, valid=None, shift=None, pitched_only=True):
+        """decoded: a DecodedBatch; song [B]: the song of every row; valid, shift, pitched_only: metric.interplay_counts'.  A song is
+        seen when one of its rows is counted (status OK).  No sync with the host."""
+        ic = metric.interplay_counts(decoded, song, valid, shift, pitched_only)
+        ok = ic.status == metric.INTERPLAY_OK                          # the rows that are not OK hold zeros
+        role = decoded.meta[:, 9].long() - 719
+        role = torch.where((role >= 0) & (role < self.ROLES - 1), role, torch.full_like(role, self.ROLES - 1))
+        self.ticks += ic.ticks.sum(0)
+        self.pairs += ic.pairs.sum(0)
+        self.role_ticks.index_add_(0, role, ic.ticks)
+        self.role_pairs.index_add_(0, role, ic.pairs)
+        song = torch.as_tensor(song).to(ok.device)
+        b = torch.arange(len(ok), device=ok.device)
+        earlier = ((song.unsqueeze(1) == song.unsqueeze(0)) & ok.unsqueeze(0) & (b.unsqueeze(0) < b.unsqueeze(1))).any(1)
+        c = ic.counts.long()
+        self.scalars += torch.stack([ok.sum(), c[:, 0].sum(), c[:, 3].sum(), (ok & ~earlier).sum()])
+        return self
+
+    def vector(self):
+        """int64 [166] on the device: ticks (9), pairs (9), ticks per role (8 x 9), pairs per role (8 x 9), SCALAR_NAMES"""
+        return torch.cat([self.ticks, self.pairs, self.role_ticks.reshape(-1), self.role_pairs.reshape(-1), self.scalars])
+
+    @classmethod
+    def ratios(cls, host):
+        """host: vector() as Python ints -> the summary, computed in float64; a ratio with an empty denominator is NaN"""
+        div = lambda a, b: float(a) / float(b) if b else float("nan")
+        host = [int(x) for x in host]
+        ticks, pairs = host[:9], host[9:18]
+        role_ticks = [host[18 + 9 * r:27 + 9 * r] for r in range(cls.ROLES)]
+        rows, notes, accompanied, songs = host[18 + 18 * cls.ROLES:]
+        sounding = sum(ticks[:7])
+        bass, melody = role_ticks[cls.BASS_ROW], role_ticks[cls.MELODY_ROW]
+        return {"rows": rows, "songs": songs, "notes": notes, "pairs": sum(pairs[:7]) // 2, "ticks": sounding // 2,
+                "dissonance": div(ticks[1] + ticks[2] + ticks[6], sounding), "unison": div(ticks[0], sounding),
+                "accompanied": div(accompanied, notes), "bass_above": div(bass[8], bass[7] + bass[8]),
+                "melody_below": div(melody[7], melody[7] + melody[8])}
+
+    def summary(self):
+        """{"rows", "songs", "notes", "pairs", "ticks", "dissonance", "unison", "accompanied", "bass_above", "melody_below"}: rows =
+        the rows counted, songs = the songs with a counted row, notes = their counted notes; pairs / ticks = the unordered pairs of
+        notes of two tracks of a song that sound together and their common ticks (every pair is seen from both rows); dissonance =
+        the ticks of interval classes 1, 2 and 6 (seconds, sevenths, the tritone) over the ticks of all seven; unison = the ticks of
+        class 0 (unisons, octaves) over the same sum; accompanied = the share of counted notes that sound together with a note of
+        another track; bass_above = of the ticks the bass rows share with a note of another pitch, those where the bass is the
+        higher; melody_below = the same for the main-melody rows and the lower.  The one device -> host copy."""
+        return self.ratios(self.vector().cpu().tolist())
+
+
+def interplay_block(s):
+    """the interplay summary of a run, in the style of harmony_block"""
+    rows, songs, pairs, notes = s["rows"], s["songs"], s["pairs"], s["notes"]
+    lines = ["", f"{' Summary: Interplay ':=^60}", f"{f' Songs: {songs} ({rows} tracks, {notes} notes) ': ^60}",
+             f"{f' Pairs sounding together: {pairs} ': ^60}"]
+    names = (("dissonance", "Dissonance"), ("unison", "Unison"), ("accompanied", "Accompanied"), ("bass_above", "Bass above"),
+             ("melody_below", "Melody below"))
+    lines += [f"{f' {label}: {s[key]:.6f} ': ^60}" for key, label in names]
+    return "\n".join(lines + [("=" * 60) + "\n"])
 
 
 def generation_block(s):

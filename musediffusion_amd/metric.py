@@ -9,7 +9,8 @@ Additions without a reference counterpart: `nearest` / `ONNC_sets` (the fused 1-
 `Controllability_Harmony` (csrc/harmony.hip) are CH, the control metric of the ComMU paper the reference never wrote: do the notes of
 a decoded piece fit the chord progression it was conditioned on.  `structure_counts` (csrc/structure.hip) are the per-bar counts
 behind H1 / H4 (pitch-class entropy of 1-bar and 4-bar windows) and GS (groove similarity) of the MusDr set: is a piece shaped like
-music over time.
+music over time.  `interplay_counts` (csrc/arrange.hip) looks at the rows of one song together: which intervals sound between the
+tracks, for how long, and which track lies below.
 
 Where this module differs from the reference, on purpose (pinned by tests/test_batch_matrix_gpu.py):
   * get_vectors never raises: status 1 = no BAR token (the reference: IndexError), 2 = a malformed note group or a row that ends
@@ -22,7 +23,7 @@ Where this module differs from the reference, on purpose (pinned by tests/test_b
 import numpy as np
 import torch
 
-from ._lib import HARMONY_ENUMS, STRUCTURE_ENUMS, check, current_stream, lib, ptr, require_device
+from ._lib import ARRANGE_ENUMS, HARMONY_ENUMS, STRUCTURE_ENUMS, check, current_stream, lib, ptr, require_device
 
 
 def get_vectors(tokens, lengths=None, note_len=128, return_status=False):
@@ -376,3 +377,65 @@ def structure_counts(decoded, valid=None, max_bars=64, return_bars=False):
     if valid is None:
         valid = decoded.status == 0
     return structure_counts_raw(decoded.notes, decoded.counts, decoded.meta, valid, max_bars, return_bars)
+
+
+# ------------------------------------------------------------------------------------------ interplay (csrc/arrange.hip), additions
+# mirror of enum mha_status (include/musehip_arrange.h)
+INTERPLAY_OK, INTERPLAY_MASKED, INTERPLAY_BAD_COUNTS, INTERPLAY_BAD_SHIFT, INTERPLAY_MIXED = (
+    ARRANGE_ENUMS["MHA_" + n] for n in ("OK", "MASKED", "BAD_COUNTS", "BAD_SHIFT", "MIXED"))
+INTERPLAY_COUNT_NAMES = ("notes", "skipped", "partners", "accompanied", "reserved_0", "reserved_1", "reserved_2", "reserved_3")
+INTERPLAY_COLUMN_NAMES = tuple("interval_class_%d" % i for i in range(7)) + ("below", "above")
+INTERPLAY_MAX_NOTES, INTERPLAY_MAX_SHIFT = 32768, 1 << 29
+DRUMS_INST = 648                                              # the inst token (meta[5]) of the drum group: its note numbers are no pitches
+
+
+class InterplayCounts:
+    """Device results of one batch (include/musehip_arrange.h): status int32 [B] (INTERPLAY_OK ...; a row that is not OK has zeros
+    everywhere), counts int32 [B, 8] in INTERPLAY_COUNT_NAMES order, pairs and ticks int64 [B, 9] in INTERPLAY_COLUMN_NAMES order: the
+    pairs (this row's note, a partner's note) that sound together and their common ticks, at most 65535 a pair."""
+
+    def __init__(self, status, counts, pairs, ticks):
+        self.status, self.counts, self.pairs, self.ticks = status, counts, pairs, ticks
+
+
+def interplay_counts_raw(notes, counts3, meta, valid=None, song=None, shift=None):
+    """mha_interplay_counts on the tensors a decode leaves: notes [B, max_notes, 4] = (start tick, end tick, pitch, velocity), counts3
+    [B, 3] = (notes, -, -), meta [B, 11], valid [B] or None (every row), song [B] int group ids or None (one song), shift [B] ticks
+    added to a row's notes or None -> InterplayCounts.  The rows of one song are partners; the rule is the header's.  ONE launch
+    whatever the batch; nothing syncs with the host."""
+    if notes.dim() != 3 or notes.shape[2] != 4:
+        raise ValueError("interplay_counts: notes [B, max_notes, 4]")
+    B, max_notes = notes.shape[0], notes.shape[1]
+    if tuple(counts3.shape) != (B, 3) or tuple(meta.shape) != (B, 11):
+        raise ValueError("interplay_counts: counts [B, 3] and meta [B, 11]")
+    for name, t in (("song", song), ("shift", shift)):
+        if t is not None and tuple(t.shape) != (B,):
+            raise ValueError("interplay_counts: %s holds one entry per row" % name)
+    if not 1 <= max_notes <= INTERPLAY_MAX_NOTES or B * max_notes > 1 << 31:
+        raise ValueError("interplay_counts: max_notes in 1..%d and B * max_notes <= 2^31 (got %d, %d)" % (INTERPLAY_MAX_NOTES, max_notes, B))
+    if B < 1:
+        raise ValueError("interplay_counts: an empty batch")
+    require_device(notes, counts3, meta, valid, song, shift)
+    dev = notes.device
+    notes, counts3, meta = (t.to(torch.int32).contiguous() for t in (notes, counts3, meta))
+    valid = _mask_i32(valid, B, dev)
+    song, shift = (None if t is None else t.to(device=dev, dtype=torch.int32).contiguous() for t in (song, shift))
+    counts = torch.empty(B, 8, device=dev, dtype=torch.int32)
+    pairs = torch.empty(B, 9, device=dev, dtype=torch.int64)
+    ticks = torch.empty(B, 9, device=dev, dtype=torch.int64)
+    status = torch.empty(B, device=dev, dtype=torch.int32)
+    check(lib().mha_interplay_counts(ptr(notes), ptr(counts3), ptr(meta), ptr(valid), ptr(song), ptr(shift), ptr(counts), ptr(pairs),
+                                     ptr(ticks), ptr(status), B, max_notes, current_stream()), "mha_interplay_counts")
+    return InterplayCounts(status, counts, pairs, ticks)
+
+
+def interplay_counts(decoded, song, valid=None, shift=None, pitched_only=True):
+    """interplay_counts_raw on a DecodedBatch (utils.decode_util.decode_tokens) whose rows `song` [B] groups into songs; valid
+    defaults to the rows that decoded (decoded.status == OK: the lists of the others hold nothing); shift: ticks per row, as
+    utils.arrange_util.align_shift makes them; pitched_only: the rows of the drum group (meta[5] == 648) are masked - a drum note
+    number is not a pitch, so no interval with it means anything."""
+    if valid is None:
+        valid = decoded.status == 0
+    if pitched_only:
+        valid = (valid != 0) & (decoded.meta[:, 5] != DRUMS_INST)
+    return interplay_counts_raw(decoded.notes, decoded.counts, decoded.meta, valid, song, shift)

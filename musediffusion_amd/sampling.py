@@ -19,7 +19,10 @@ row is not lost to one token in the wrong place; the in-loop clamp (denoised_fn_
 (gu.constrain_region_tokens, csrc/region.hip), so that the splice drops no token of a broken note.  Nor is `structure=True` of the
 three loops: the batch's one decode also goes through evaluation.StructureTotals (csrc/structure.hip) and the report says how the
 pieces are shaped over time - pitch-class entropy of 1-bar and 4-bar windows, groove similarity of the bars - next to the same
-numbers of the ground truth (modification, infill) or of a summary the caller made from a training set (generation)."""
+numbers of the ground truth (modification, infill) or of a summary the caller made from a training set (generation).  Nor are
+`arrange` / `run_arrangement`: the batch is the tracks of several songs over one chord progression (utils/arrange_util.py), sampled
+by `generate` as it is; the loop aligns the decoded tracks of a song, writes each complete song as ONE multitrack file and reports how
+the tracks fit each other (evaluation.InterplayTotals, csrc/arrange.hip)."""
 import contextlib
 import io
 import os
@@ -30,7 +33,7 @@ import torch
 
 from . import evaluation, sharding
 from .models.rounding import denoised_fn_round
-from .utils import decode_util as du, grammar_util as gu
+from .utils import arrange_util as au, decode_util as du, grammar_util as gu
 
 
 def _prepare(model, cond, device):
@@ -211,7 +214,9 @@ class SamplingReport:
     rounding='region', `region` (gu.RegionResult.describe over all batches: rows per status, masked slots, notes, pads, segments); a run with
     constrained=True adds `constrained` (gu.ConstrainResult.describe over all batches: rows per status, Bars and notes placed); a run with
     structure=True adds `structure` ({"generated"[, "reference", "gap"]}: evaluation.StructureTotals summaries and their
-    evaluation.structure_gap, or None when no batch ran)."""
+    evaluation.structure_gap, or None when no batch ran); run_arrangement adds `songs` (the songs written, or that would have been
+    without an output directory) and `interplay` (evaluation.InterplayTotals.summary(), or None with interplay=False or when no
+    batch ran) - its total_valid_count counts the tracks that decoded."""
 
     def __init__(self, total_valid_count, totals, summary, batches):
         self.total_valid_count, self.totals, self.summary, self.batches = total_valid_count, totals, summary, batches
@@ -481,4 +486,68 @@ def run_generation(model, diffusion, midi_meta_dict, *, batch_size, seq_len, num
             log(_constrained_block(report.constrained))
     if structure:
         report.structure = _structure_report(shape, None, structure_reference, log) if shape is not None else None
+    return report
+
+
+# ------------------------------------------------------------------------------------------------ from single tracks to songs
+@torch.no_grad()
+def arrange(model, diffusion, base_meta, tracks, n_songs, seq_len, **generate_keywords):
+    """`generate` on au.arrangement_batch(base_meta, tracks, n_songs, seq_len), nothing else: every row is one track of one song,
+    the rows of a song share the chord progression, tempo, key and time signature of `base_meta` and differ in what `tracks`
+    overrides (inst, track_role, pitch_range, min_velocity, max_velocity).  generate_keywords: `generate`'s (step, noise, solver,
+    constrained, ...).  -> (generate's result, song [B], track [B], cond)."""
+    device = model.word_embedding.weight.device
+    cond, song, track = au.arrangement_batch(base_meta, tracks, n_songs, seq_len, device)
+    return generate(model, diffusion, cond, **generate_keywords), song, track, cond
+
+
+@torch.no_grad()
+def run_arrangement(model, diffusion, base_meta, tracks, *, n_songs, seq_len, num_songs, out_dir, step=None, keep_partial=False,
+                    interplay=True, max_batches=None, sampler=None, clip_denoised=True, top_p=1, clamp_step=0, log=print, device="cuda",
+                    solver="ddim", solver_order=2):
+    """run_generation for songs: ONE au.arrangement_batch of n_songs songs (len(tracks) rows each), sampled again and again until
+    num_songs songs are complete (or max_batches batches ran).  Per batch the sampler (`sampler(cond)`, default `generate`, sharded
+    when a process group is up), ONE decode without strict validation, au.align_shift (torch operations) and, with `interplay`, one
+    more library launch (evaluation.InterplayTotals.update with the shifts; drum rows masked).  A song is complete iff every one of
+    its tracks decoded OK; complete songs are written by au.write_song as song_{n:0>7}.midi, n counting on over the run, with the
+    chord markers of the song's first track (out_dir None: decoded and counted, nothing written).  keep_partial: songs with at least
+    two decoded tracks are written too, from the tracks that decoded, and count.  Rows of a fatal status raise as in run_generation.
+    Returns a SamplingReport: total_valid_count = the tracks that decoded, batches, `songs` = the songs that count and `interplay` =
+    the summary from one more device -> host copy after the loop, logged as evaluation.interplay_block (None without `interplay` or
+    when no batch ran)."""
+    loop = _solver(solver, solver_order)
+    if sampler is None:
+        sampler = lambda cond: generate(model, diffusion, cond, step, clip_denoised, top_p, clamp_step, sharded=True, **loop)  # noqa: E731
+    cond, song, _ = au.arrangement_batch(base_meta, tracks, n_songs, seq_len, device)
+    T = len(tracks)
+    write = out_dir is not None and sharding.rank() == 0
+    if write:
+        os.makedirs(out_dir, exist_ok=True)
+    songs, valid_rows, batch_index, fit = 0, 0, 0, None
+    while songs < num_songs and (max_batches is None or batch_index < max_batches):
+        tokens = sampler(cond)
+        dec = du.decode_tokens(tokens, cond["input_mask"].to(tokens.device), strict_validation=False)
+        shift = au.align_shift(dec, song.to(tokens.device))
+        if interplay:
+            fit = (fit or evaluation.InterplayTotals(tokens.device)).update(dec, song, shift=shift)
+        rows, shifts = dec.cpu(), shift.cpu().tolist()
+        evaluation.MetricTotals.raise_if_fatal(_fatal_status(rows))
+        for s in range(n_songs):
+            ok = [b for b in range(s * T, (s + 1) * T) if int(rows.status[b]) == du.OK]
+            valid_rows += len(ok)
+            if len(ok) < (min(2, T) if keep_partial else T):
+                continue
+            if write:
+                au.write_song(os.path.join(out_dir, f"song_{songs:0>7}.midi"), [rows.notes[b] for b in ok], rows.chords[ok[0]] + [shifts[ok[0]], 0],
+                              rows.meta[ok], [shifts[b] for b in ok], [au.track_name(rows.meta[b], b - s * T) for b in ok])
+            songs += 1
+        log(f"### Batch {batch_index}: {songs} songs so far")
+        batch_index += 1
+    if out_dir is not None:
+        log(f"### Written the decoded output to {out_dir}")
+    report = SamplingReport(valid_rows, None, None, batch_index)
+    report.songs = songs
+    report.interplay = fit.summary() if fit is not None else None
+    if fit is not None:
+        log(evaluation.interplay_block(report.interplay))
     return report

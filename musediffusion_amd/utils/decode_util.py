@@ -149,6 +149,18 @@ def decode_tokens(tokens, input_mask, strict_validation=False, ld_out=None, max_
     return out
 
 
+def first_bar_shift(decoded):
+    """int64 [B]: 1 where the first token of the restored row that the decoder keeps (2..559) is not BAR, else 0.  The decoder counts a
+    BAR only behind the row's first kept token, so in such a row the notes in front of the first BAR fill bar 0 and the bar that BAR
+    opens is bar 1, while an infill plan numbers the bars from the first BAR (bar 0) and gives the tokens before it to no bar:
+    a note's start / ticks_per_bar is its infill ordinal plus this shift."""
+    r = decoded.restored
+    idx = torch.arange(r.shape[1], device=r.device).unsqueeze(0)
+    kept = (r >= 2) & (r <= 559) & (idx < decoded.lengths.unsqueeze(1))
+    first = torch.where(kept.any(1), r.gather(1, kept.int().argmax(1, keepdim=True)).squeeze(1), torch.full_like(r[:, 0], 2))
+    return (first != 2).long()
+
+
 def _vlq(n):
     out = [n & 0x7F]
     n >>= 7
@@ -168,11 +180,9 @@ def _track(events):
     return b"MTrk" + struct.pack(">I", len(body)) + body
 
 
-def write_midi(path, notes, chords, meta):
-    """Standard MIDI File, format 1, 480 ticks per beat, no third-party package.  Track 0: tempo = (bpm token - 560) * 5 BPM, time
-    signature, key signature, the chord markers as text (CHORD_NAMES); track 1: program 0 on channel 0 and the notes
-    (start tick, end tick, pitch, velocity).  What encoder_utils.write_midi puts into its miditoolkit container; byte equality
-    with miditoolkit's dump is not claimed (the package is not a dependency) - the content is."""
+def conductor_track(chords, meta):
+    """track 0 of write_midi as an MTrk chunk: tempo, time signature, key signature and the chord markers (shared with
+    utils.arrange_util.write_song)"""
     bpm = (int(meta[0]) - 560) * 5
     num, den = TIME_SIGNATURES[int(meta[2]) - 627]
     key = int(meta[1]) - 602
@@ -186,12 +196,27 @@ def write_midi(path, notes, chords, meta):
     for k, (tick, tok) in enumerate(np.asarray(chords).reshape(-1, 2).tolist()):
         text = CHORD_NAMES[tok - 195].encode()
         t0.append((tick, 3 + k, b"\xff\x06" + _vlq(len(text)) + text))
-    t1 = [(0, 0, b"\xc0\x00")]
+    return _track(t0)
+
+
+def note_events(notes, channel=0):
+    """the note-on / note-off events of a note track in write_midi's order: at one tick, offs go before ons"""
+    out = []
     for k, (start, end, pitch, vel) in enumerate(np.asarray(notes).reshape(-1, 4).tolist()):
-        t1.append((start, 2 + 2 * k + 1, bytes([0x90, pitch, vel])))
-        t1.append((end, 1, bytes([0x80, pitch, 0])))                                 # at one tick, offs go before ons
+        out.append((start, 2 + 2 * k + 1, bytes([0x90 | channel, pitch, vel])))
+        out.append((end, 1, bytes([0x80 | channel, pitch, 0])))
+    return out
+
+
+def write_midi(path, notes, chords, meta):
+    """Standard MIDI File, format 1, 480 ticks per beat, no third-party package.  Track 0: tempo = (bpm token - 560) * 5 BPM, time
+    signature, key signature, the chord markers as text (CHORD_NAMES); track 1: program 0 on channel 0 and the notes
+    (start tick, end tick, pitch, velocity).  What encoder_utils.write_midi puts into its miditoolkit container; byte equality
+    with miditoolkit's dump is not claimed (the package is not a dependency) - the content is."""
+    t0 = conductor_track(chords, meta)
+    t1 = [(0, 0, b"\xc0\x00")] + note_events(notes)
     with open(path, "wb") as f:
-        f.write(b"MThd" + struct.pack(">IHHH", 6, 1, 2, TICKS_PER_BEAT) + _track(t0) + _track(t1))
+        f.write(b"MThd" + struct.pack(">IHHH", 6, 1, 2, TICKS_PER_BEAT) + t0 + _track(t1))
 
 
 def _read_vlq(data, i):
@@ -237,9 +262,11 @@ def read_midi(path):
     return division, np.zeros((0, 4), np.int32)
 
 
-def _read_track(data):
+def _read_track(data, info=None):
     """the body of one MTrk chunk -> ([start, end or None, pitch, velocity] per note in start order, the track's last tick).  Every
-    read is inside `data`: an event that runs past the chunk raises IndexError, which read_midi reports as its ValueError."""
+    read is inside `data`: an event that runs past the chunk raises IndexError, which read_midi reports as its ValueError.
+    info: a dict that takes the track's "name" (its first FF 03 event), "program" (its first program change) and "channel" (of its
+    first channel message) - utils.arrange_util.read_song."""
     i, end = 0, len(data)
     now, status, running, open_notes, notes = 0, 0, 0, {}, []
     while i < end:
@@ -252,16 +279,25 @@ def _read_track(data):
         else:
             status = running
         if status == 0xFF:                                                      # meta event: type, length, data
+            kind = data[i]
             n, i = _read_vlq(data, i + 1)
+            if info is not None and kind == 3 and i + n <= end:
+                info.setdefault("name", bytes(data[i:i + n]).decode("utf-8", "replace"))
             i += n
         elif status in (0xF0, 0xF7):                                             # system exclusive
             n, i = _read_vlq(data, i)
             i += n
         elif status >> 4 in (0xC, 0xD):
+            if info is not None:
+                info.setdefault("channel", status & 0xF)
+                if status >> 4 == 0xC:
+                    info.setdefault("program", data[i])
             i += 1
         elif status >> 4 in (0x8, 0x9):
             key, vel = (status & 0xF, data[i]), data[i + 1]
             i += 2
+            if info is not None:
+                info.setdefault("channel", status & 0xF)
             if status >> 4 == 0x9 and vel > 0:
                 open_notes.setdefault(key, []).append(len(notes))
                 notes.append([now, None, key[1], vel])
