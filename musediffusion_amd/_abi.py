@@ -1,6 +1,4 @@
-"""The C ABI as ctypes, read from the headers that define it (include/musehip.h, include/musehip_dbg.h, include/musehip_data.h,
-include/musehip_eval.h, include/musehip_stats.h, include/musehip_infill.h, include/musehip_harmony.h, include/musehip_grammar.h,
-include/musehip_region.h, include/musehip_solver.h, include/musehip_structure.h, include/musehip_arrange.h).
+"""The C ABI as ctypes, read from the headers that define it: those _lib.HEADERS names, and include/musehip_dbg.h.
 
 `load(name)` gives the header's enumerators (name -> int), its structs (name -> ctypes.Structure class) and its prototypes
 (name -> (restype, argtypes)).  The reader knows the C these headers are written in and nothing more: a declaration it does not

@@ -1,14 +1,11 @@
-"""ctypes binding of libmusehip.so (C ABI: include/musehip.h, include/musehip_data.h for the dataset loader and
-include/musehip_eval.h for the evaluation of sampled batches, include/musehip_stats.h for the pair statistics of a set,
-include/musehip_infill.h for the infill mask and splice, include/musehip_harmony.h for the chord-fit counts,
-include/musehip_grammar.h for the grammar-constrained rounding, include/musehip_region.h for the rounding of infill regions,
-include/musehip_solver.h for the multistep DPM-Solver++ reverse step, include/musehip_structure.h for the structure counts,
-include/musehip_arrange.h for the interplay counts of the tracks of a song).
+"""ctypes binding of libmusehip.so.  The C ABI is the headers under include/ that HEADERS names: musehip.h for the model side and one
+header per entry-point family beside it, each with a prefix of its own (mhd_, mhe_, ...) and exported by both libraries.
 
 There is no fallback: `lib()` raises if the shared library is absent or does not export the
-symbols the header declares.  Build it with `python -c "import __graft_entry__ as g; g.build()"`
+symbols the headers declare.  Build it with `python -c "import __graft_entry__ as g; g.build()"`
 or `make -C musediffusion_amd/csrc`.
 """
+import collections
 import ctypes as C
 import os
 
@@ -21,19 +18,32 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libmusehip.so")
 if os.environ.get("MUSEHIP_AB") == "1" and os.environ.get("MUSEHIP_LIB"):
     LIB_PATH = os.environ["MUSEHIP_LIB"]
 
-# The header is the single source of the ABI: signatures, struct layouts and enum values are read from it (_abi.py), not restated here
-_H = _abi.load("musehip.h")
-_DBG_H = _abi.load("musehip_dbg.h", _H)
-_DATA_H = _abi.load("musehip_data.h", _H)
-_EVAL_H = _abi.load("musehip_eval.h", _H)
-_STATS_H = _abi.load("musehip_stats.h", _H)
-_INFILL_H = _abi.load("musehip_infill.h", _H)
-_HARMONY_H = _abi.load("musehip_harmony.h", _H)
-_GRAMMAR_H = _abi.load("musehip_grammar.h", _H)
-_REGION_H = _abi.load("musehip_region.h", _H)
-_SOLVER_H = _abi.load("musehip_solver.h", _H)
-_STRUCTURE_H = _abi.load("musehip_structure.h", _H)
-_ARRANGE_H = _abi.load("musehip_arrange.h", _H)
+# The headers both libraries export, in load order: musehip.h, whose types the others use, then one per entry-point family.  A new
+# family is one more name here ("Adding an entry-point family")
+HEADERS = ("musehip.h", "musehip_data.h", "musehip_eval.h", "musehip_stats.h", "musehip_infill.h", "musehip_harmony.h", "musehip_grammar.h",
+           "musehip_region.h", "musehip_solver.h", "musehip_structure.h", "musehip_arrange.h")
+# The headers are the single source of the ABI: signatures, struct layouts and enum values are read from them (_abi.py), not restated here.
+# header name -> its .protos (name -> (restype, argtypes); a pointer argument is c_void_p, char*: c_char_p), .structs and .enums
+_H = _abi.load(HEADERS[0])
+ABI = {HEADERS[0]: _H, **{name: _abi.load(name, _H) for name in HEADERS[1:]}}
+
+
+def _merged(tables):
+    out = {}
+    for protos in tables:
+        twice = set(out) & set(protos)
+        if twice:
+            raise _abi.AbiError("declared by two headers: %s" % ", ".join(sorted(twice)))
+        out.update(protos)
+    return out
+
+
+# every symbol libmusehip.so exports
+PRODUCT_SIGNATURES = _merged(h.protos for h in ABI.values())
+# every symbol include/musehip.h declares
+SIGNATURES = _H.protos
+# include/musehip_dbg.h: exported by libmusehip_dbg.so only (A/B switches, ablation knobs, diagnostics)
+DBG_SIGNATURES = _abi.load("musehip_dbg.h", _H).protos
 
 MH_ERR_INVALID, MH_ERR_HIP, MH_ERR_UNSUPPORTED = (_H.enums["MH_ERR_" + n] for n in ("INVALID", "HIP", "UNSUPPORTED"))
 MH_F32, MH_BF16, MH_BF16X3, MH_F16X3 = (_H.enums["MH_" + n] for n in ("F32", "BF16", "BF16X3", "F16X3"))
@@ -51,41 +61,8 @@ TrainLayer = _H.structs["mh_train_layer"]
 LayerWeights = _H.structs["mh_layer_weights"]
 LnDefer = _H.structs["mh_ln_defer"]
 Denoiser = _H.structs["mh_denoiser"]
-
-# name -> (restype, argtypes): every symbol include/musehip.h declares; a pointer argument is c_void_p (char*: c_char_p)
-SIGNATURES = _H.protos
-# include/musehip_dbg.h: exported by libmusehip_dbg.so only (A/B switches, ablation knobs, diagnostics)
-DBG_SIGNATURES = _DBG_H.protos
-# include/musehip_data.h: the dataset loader's mhd_* entry points and their status enums, exported by both libraries
-DATA_SIGNATURES = _DATA_H.protos
-DATA_ENUMS = _DATA_H.enums
-# include/musehip_eval.h: the mhe_* entry points (fused MSIM nearest neighbour), exported by both libraries
-EVAL_SIGNATURES = _EVAL_H.protos
-EVAL_ENUMS = _EVAL_H.enums
-# include/musehip_stats.h: the mhs_* entry points (pair statistics under MSIM), exported by both libraries
-STATS_SIGNATURES = _STATS_H.protos
-# include/musehip_infill.h: the mhi_* entry points (infill mask and splice) and enum mhi_status, exported by both libraries
-INFILL_SIGNATURES = _INFILL_H.protos
-INFILL_ENUMS = _INFILL_H.enums
-# include/musehip_harmony.h: the mhh_* entry point (chord-fit counts of decoded rows) and enum mhh_status, exported by both libraries
-HARMONY_SIGNATURES = _HARMONY_H.protos
-HARMONY_ENUMS = _HARMONY_H.enums
-# include/musehip_grammar.h: the mhg_* entry points (class winners, row Viterbi), struct mhg_classes and its enums, exported by both libraries
-GRAMMAR_SIGNATURES = _GRAMMAR_H.protos
-GRAMMAR_ENUMS = _GRAMMAR_H.enums
-GrammarClasses = _GRAMMAR_H.structs["mhg_classes"]
-# include/musehip_region.h: the mhr_* entry point (whole-note rounding of an infill plan's regions) and enum mhr_status, exported by both libraries
-REGION_SIGNATURES = _REGION_H.protos
-REGION_ENUMS = _REGION_H.enums
-# include/musehip_solver.h: the mhv_* entry point (DPM-Solver++(2M) update of a reverse step) and struct mhv_solver_coef, exported by both libraries
-SOLVER_SIGNATURES = _SOLVER_H.protos
-SolverCoef = _SOLVER_H.structs["mhv_solver_coef"]
-# include/musehip_structure.h: the mhm_* entry point (per-bar pitch-class entropy and groove counts of decoded rows) and enum mhm_status, exported by both libraries
-STRUCTURE_SIGNATURES = _STRUCTURE_H.protos
-STRUCTURE_ENUMS = _STRUCTURE_H.enums
-# include/musehip_arrange.h: the mha_* entry points (interplay counts of the rows of a song, the tile they are staged in) and enum mha_status, exported by both libraries
-ARRANGE_SIGNATURES = _ARRANGE_H.protos
-ARRANGE_ENUMS = _ARRANGE_H.enums
+GrammarClasses = ABI["musehip_grammar.h"].structs["mhg_classes"]
+SolverCoef = ABI["musehip_solver.h"].structs["mhv_solver_coef"]
 
 _lib = None
 _handles = {}
@@ -126,7 +103,7 @@ def lib():
     switched to the debug build (use_debug_library / debug_library)."""
     global _lib
     if _lib is None:
-        _lib = _load(LIB_PATH, {**SIGNATURES, **DATA_SIGNATURES, **EVAL_SIGNATURES, **STATS_SIGNATURES, **INFILL_SIGNATURES, **HARMONY_SIGNATURES, **GRAMMAR_SIGNATURES, **REGION_SIGNATURES, **SOLVER_SIGNATURES, **STRUCTURE_SIGNATURES, **ARRANGE_SIGNATURES}, "libmusehip.so")
+        _lib = _load(LIB_PATH, PRODUCT_SIGNATURES, "libmusehip.so")
     return _lib
 
 
@@ -136,8 +113,8 @@ def use_debug_library(on=True):
     the product never calls this.  Each library has its own switch state; objects made under one (captured graphs, engines' arenas)
     are plain HIP objects and stay valid under the other."""
     global _lib
-    _lib = (_load(DBG_LIB_PATH, {**SIGNATURES, **DATA_SIGNATURES, **EVAL_SIGNATURES, **STATS_SIGNATURES, **INFILL_SIGNATURES, **HARMONY_SIGNATURES, **GRAMMAR_SIGNATURES, **REGION_SIGNATURES, **SOLVER_SIGNATURES, **STRUCTURE_SIGNATURES, **ARRANGE_SIGNATURES, **DBG_SIGNATURES}, "libmusehip_dbg.so") if on else
-            _load(LIB_PATH, {**SIGNATURES, **DATA_SIGNATURES, **EVAL_SIGNATURES, **STATS_SIGNATURES, **INFILL_SIGNATURES, **HARMONY_SIGNATURES, **GRAMMAR_SIGNATURES, **REGION_SIGNATURES, **SOLVER_SIGNATURES, **STRUCTURE_SIGNATURES, **ARRANGE_SIGNATURES}, "libmusehip.so"))
+    _lib = (_load(DBG_LIB_PATH, _merged((PRODUCT_SIGNATURES, DBG_SIGNATURES)), "libmusehip_dbg.so") if on else
+            _load(LIB_PATH, PRODUCT_SIGNATURES, "libmusehip.so"))
     return _lib
 
 
@@ -167,6 +144,37 @@ def ptr(t):
 def current_stream():
     import torch
     return torch.cuda.current_stream().cuda_stream
+
+
+LaunchRecord = collections.namedtuple("LaunchRecord", "kernel detail grid block stream ms")
+
+
+def record_launches(fn):
+    """fn() between mh_profile_start and mh_profile_stop -> one LaunchRecord per kernel the library launched meanwhile, in launch order.
+    The fields are those of the report line (include/musehip.h): kernel text as launched, detail, blocks and threads in x, stream, and
+    milliseconds between the two events around the launch.  The recorder's events cannot be captured, so this refuses inside a graph
+    capture; it measures and tests, the product never calls it."""
+    import torch
+    L = lib()
+    if torch.cuda.is_current_stream_capturing():
+        raise MuseHipError("the launch recorder must not run inside a graph capture")
+    torch.cuda.synchronize()
+    check(L.mh_profile_start(), "mh_profile_start")
+    try:
+        fn()
+    finally:
+        # mh_profile_stop keeps its records until the next start and returns the bytes the whole report needs, whatever it was given: the
+        # first call stops the recorder and asks, the second fetches - no size to guess for the longest run
+        need = L.mh_profile_stop(None, 0)
+        buf = C.create_string_buffer(max(need, 1))
+        got = L.mh_profile_stop(buf, len(buf))
+    if not 0 < need == got:
+        raise MuseHipError("mh_profile_stop failed (%d, then %d)" % (need, got))
+    out = []
+    for line in buf.value.decode().splitlines():
+        kernel, detail, grid, block, stream, ms = line.split("\t")
+        out.append(LaunchRecord(kernel, detail, int(grid), int(block), stream, float(ms)))
+    return out
 
 
 def require_device(*tensors):

@@ -15,12 +15,12 @@ import os
 import numpy as np
 import torch
 
-from .._lib import DATA_ENUMS, check, current_stream, lib, ptr, require_device
+from .._lib import ABI, check, current_stream, lib, ptr, require_device
 from .corruption import Corruptions
 from .wrapper import _pad, collate_batches, gather_rows, to_ragged
 
 # enum mhd_augment_status (include/musehip_data.h)
-AUGMENT_OK, NOT_ORIGIN, PITCH_RANGE, BAD_ROW = (DATA_ENUMS["MHD_AUGMENT_" + n] for n in ("OK", "NOT_ORIGIN", "PITCH_RANGE", "BAD_ROW"))
+AUGMENT_OK, NOT_ORIGIN, PITCH_RANGE, BAD_ROW = (ABI["musehip_data.h"].enums["MHD_AUGMENT_" + n] for n in ("OK", "NOT_ORIGIN", "PITCH_RANGE", "BAD_ROW"))
 # commu/preprocessor/utils/constants.py:28-29 and augment.py:94-97: key_change in range(-6, 6), bpm_change in range(-2, 3)
 KEY_CHANGES, BPM_CHANGES = range(-6, 6), range(-2, 3)
 FILTER_BELOW = 2096                    # preprocess.py:116: rows are filtered by length only when seq_len < 2096

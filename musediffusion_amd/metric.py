@@ -23,7 +23,7 @@ Where this module differs from the reference, on purpose (pinned by tests/test_b
 import numpy as np
 import torch
 
-from ._lib import ARRANGE_ENUMS, HARMONY_ENUMS, STRUCTURE_ENUMS, check, current_stream, lib, ptr, require_device
+from ._lib import ABI, check, current_stream, lib, ptr, require_device
 
 
 def get_vectors(tokens, lengths=None, note_len=128, return_status=False):
@@ -244,7 +244,7 @@ def diversity(vec, valid=None, groups=None):
 
 # ------------------------------------------------------------------------------------------ chord fit (csrc/harmony.hip), additions
 # mirror of enum mhh_status (include/musehip_harmony.h)
-HARMONY_OK, HARMONY_MASKED, HARMONY_BAD_META, HARMONY_BAD_COUNTS = (HARMONY_ENUMS["MHH_" + n] for n in ("OK", "MASKED", "BAD_META", "BAD_COUNTS"))
+HARMONY_OK, HARMONY_MASKED, HARMONY_BAD_META, HARMONY_BAD_COUNTS = (ABI["musehip_harmony.h"].enums["MHH_" + n] for n in ("OK", "MASKED", "BAD_META", "BAD_COUNTS"))
 HARMONY_COUNT_NAMES = ("notes", "judged", "chord_tones", "scale_tones", "ticks", "judged_ticks", "chord_tone_ticks", "bars_used")
 HARMONY_MAX_NOTES, HARMONY_MAX_CHORDS, HARMONY_MAX_BARS = 32768, 4096, 512
 
@@ -302,7 +302,7 @@ def Controllability_Harmony(decoded, valid=None):
 
 # ------------------------------------------------------------------------------------------ structure (csrc/structure.hip), additions
 # mirror of enum mhm_status (include/musehip_structure.h)
-STRUCTURE_OK, STRUCTURE_MASKED, STRUCTURE_BAD_META, STRUCTURE_BAD_COUNTS = (STRUCTURE_ENUMS["MHM_" + n] for n in ("OK", "MASKED", "BAD_META", "BAD_COUNTS"))
+STRUCTURE_OK, STRUCTURE_MASKED, STRUCTURE_BAD_META, STRUCTURE_BAD_COUNTS = (ABI["musehip_structure.h"].enums["MHM_" + n] for n in ("OK", "MASKED", "BAD_META", "BAD_COUNTS"))
 STRUCTURE_COUNT_NAMES = ("notes", "skipped", "bars_used", "bars_with_notes", "pitch_classes", "distinct_pitches", "lowest_pitch",
                          "highest_pitch", "onsets", "pairs", "diff", "slots_per_bar", "windows_1", "windows_4", "reserved_0", "reserved_1")
 STRUCTURE_BAR_NAMES = ("notes", "onset_mask", "lowest_pitch", "highest_pitch") + tuple("pitch_class_%d" % p for p in range(12))
@@ -382,7 +382,7 @@ def structure_counts(decoded, valid=None, max_bars=64, return_bars=False):
 # ------------------------------------------------------------------------------------------ interplay (csrc/arrange.hip), additions
 # mirror of enum mha_status (include/musehip_arrange.h)
 INTERPLAY_OK, INTERPLAY_MASKED, INTERPLAY_BAD_COUNTS, INTERPLAY_BAD_SHIFT, INTERPLAY_MIXED = (
-    ARRANGE_ENUMS["MHA_" + n] for n in ("OK", "MASKED", "BAD_COUNTS", "BAD_SHIFT", "MIXED"))
+    ABI["musehip_arrange.h"].enums["MHA_" + n] for n in ("OK", "MASKED", "BAD_COUNTS", "BAD_SHIFT", "MIXED"))
 INTERPLAY_COUNT_NAMES = ("notes", "skipped", "partners", "accompanied", "reserved_0", "reserved_1", "reserved_2", "reserved_3")
 INTERPLAY_COLUMN_NAMES = tuple("interval_class_%d" % i for i in range(7)) + ("below", "above")
 INTERPLAY_MAX_NOTES, INTERPLAY_MAX_SHIFT = 32768, 1 << 29

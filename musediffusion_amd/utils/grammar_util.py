@@ -12,18 +12,19 @@ each - so that utils/infill_util.splice_infill finds whole notes in the region a
 import torch
 
 from .. import ops
-from .._lib import GRAMMAR_ENUMS, REGION_ENUMS, check, current_stream, lib, ptr, require_device
+from .._lib import ABI, check, current_stream, lib, ptr, require_device
 
 # mirror of enum mhg_status / enum mhg_bars (include/musehip_grammar.h)
+_GRAMMAR = ABI["musehip_grammar.h"].enums
 (CONSTRAIN_OK, CONSTRAIN_BAD_MASK, CONSTRAIN_NO_CHORDS, CONSTRAIN_TOO_MANY_BARS, CONSTRAIN_BAD_BOUNDS, CONSTRAIN_NO_ROOM,
- CONSTRAIN_NONFINITE) = (GRAMMAR_ENUMS["MHG_" + n] for n in ("OK", "BAD_MASK", "NO_CHORDS", "TOO_MANY_BARS", "BAD_BOUNDS", "NO_ROOM",
+ CONSTRAIN_NONFINITE) = (_GRAMMAR["MHG_" + n] for n in ("OK", "BAD_MASK", "NO_CHORDS", "TOO_MANY_BARS", "BAD_BOUNDS", "NO_ROOM",
                                                             "NONFINITE"))
 CONSTRAIN_STATUS_NAMES = ("ok", "bad_mask", "no_chords", "too_many_bars", "bad_bounds", "no_room", "nonfinite")
-BARS_POLICY = {"exact": GRAMMAR_ENUMS["MHG_BARS_EXACT"], "decodable": GRAMMAR_ENUMS["MHG_BARS_DECODABLE"]}
+BARS_POLICY = {"exact": _GRAMMAR["MHG_BARS_EXACT"], "decodable": _GRAMMAR["MHG_BARS_DECODABLE"]}
 COUNT_NAMES = ("bars", "notes", "through_eos")
 # mirror of enum mhr_status (include/musehip_region.h)
 REGION_OK, REGION_NOT_PLANNED, REGION_BAD_PLAN, REGION_NONFINITE, REGION_NO_ROOM = (
-    REGION_ENUMS["MHR_" + n] for n in ("OK", "NOT_PLANNED", "BAD_PLAN", "NONFINITE", "NO_ROOM"))
+    ABI["musehip_region.h"].enums["MHR_" + n] for n in ("OK", "NOT_PLANNED", "BAD_PLAN", "NONFINITE", "NO_ROOM"))
 REGION_STATUS_NAMES = ("ok", "not_planned", "bad_plan", "nonfinite", "no_room")
 REGION_COUNT_NAMES = ("masked", "notes", "pads", "segments")
 

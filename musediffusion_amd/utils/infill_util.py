@@ -7,11 +7,11 @@ tokens bit for bit, inside it only whole (position, velocity, pitch, duration) n
 read back.  sampling.infill / sampling.run_infill drive the existing generate / modify paths with them."""
 import torch
 
-from .._lib import INFILL_ENUMS, check, current_stream, lib, ptr
+from .._lib import ABI, check, current_stream, lib, ptr
 
 # mirror of enum mhi_status (include/musehip_infill.h)
 INFILL_OK, INFILL_NO_EOS, INFILL_BAD_MASK, INFILL_BAD_RANGE, INFILL_OVERFLOW = (
-    INFILL_ENUMS["MHI_" + n] for n in ("OK", "NO_EOS", "BAD_MASK", "BAD_RANGE", "OVERFLOW"))
+    ABI["musehip_infill.h"].enums["MHI_" + n] for n in ("OK", "NO_EOS", "BAD_MASK", "BAD_RANGE", "OVERFLOW"))
 INFILL_STATUS_MESSAGE = {
     INFILL_OK: "ok",
     INFILL_NO_EOS: "NO EOS TOKEN behind the prefix",

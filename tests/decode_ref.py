@@ -285,3 +285,15 @@ def make_batch(seed, L, kinds=BATCH_KINDS):
     for b, kind in enumerate(kinds):
         toks[b], masks[b] = make_row(g, L, kind)
     return toks, masks, kinds
+
+
+def make_dense_rows(g, B, L, n_bars, notes_per_bar):
+    """-> tokens [B, L], masks [B, L] (int32): B clean rows of n_bars full bars with one chord each - the batch tools/ time on"""
+    toks, masks = np.zeros((B, L), np.int32), np.zeros((B, L), np.int32)
+    for b in range(B):
+        meta, chord = make_meta(g, n_bars, 0)
+        row = meta + chord + [0] + make_notes(g, n_bars, notes_per_bar)
+        assert len(row) <= L, (len(row), L)
+        toks[b, :len(row)] = row
+        masks[b, len(meta) + len(chord) + 1:] = 1
+    return toks, masks

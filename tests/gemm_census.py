@@ -2,13 +2,11 @@
 
 * `philox7` / `dense_keep`: the dense dropout sites' keep flags restated on the host (numpy) - Philox4x32-7 keyed by the seed at counter
   ((row N + col) / 8, offset), 16 bits per element (csrc/common.h: drop_keep8).
-* `record` (`record_family` for another kernel family: tests/attention_census.py): runs a callable with the library's per-launch recorder on (mh_profile_start / mh_profile_stop) and returns the GEMM-family
+* `record` (`record_family` for another kernel family: tests/attention_census.py): runs a callable with the library's per-launch recorder on (_lib.record_launches) and returns the GEMM-family
   launches as census keys: the kernel's template text as launched (it carries EPI, ACT, the epilogue form and the DMA bits) plus the
   `tile=` field of the launch note (which config `C` stood for).  Never call it inside a hipGraph capture.
 * `WORKLOADS`: the eager runs the census records, at the shapes bench.py uses (dispatch depends on M); `run(dev, rec)` records with `rec`
   (default: `record`)."""
-import ctypes
-
 import numpy as np
 
 GEMM_FAMILY = ("gemm_kernel", "gemm_big_kernel", "gemm_strip_kernel", "gemm_tn_kernel", "split_gemm_kernel", "split_gemm_ln_kernel")
@@ -66,29 +64,9 @@ def record(fn):
 def record_family(fn, key_of):
     """fn() with the per-launch recorder on -> [(key, note, grid)] of the launches `key_of(kernel text, note)` gives a key (not None), in
     launch order; grid = blocks in x, as launched"""
-    import torch
     from musediffusion_amd import _lib
-    lib = _lib.lib()
-    assert not torch.cuda.is_current_stream_capturing(), "the launch recorder must not run inside a graph capture"
-    torch.cuda.synchronize()
-    _lib.check(lib.mh_profile_start(), "mh_profile_start")
-    try:
-        fn()
-    finally:
-        buf = ctypes.create_string_buffer(1 << 24)
-        need = lib.mh_profile_stop(buf, len(buf))
-    assert 0 < need <= len(buf), need
-    return _parse(buf.value.decode(), key_of)
-
-
-def _parse(text, key_of=census_key):
-    out = []
-    for line in text.splitlines():
-        kernel, note, grid = line.split("\t")[:3]
-        k = key_of(kernel, note)
-        if k is not None:
-            out.append((k, note, int(grid)))
-    return out
+    keyed = ((key_of(r.kernel, r.detail), r) for r in _lib.record_launches(fn))
+    return [(k, r.detail, r.grid) for k, r in keyed if k is not None]
 
 
 # ------------------------------------------------------------------------------------------------------------- census workloads

@@ -1,12 +1,10 @@
 """CPU: the evaluation end of the sampling run without a device.  tests/evaluate_ref.py (the numpy restatement of the fused
 nearest-neighbour kernel and of evaluate_batch / MetricTotals) against every record of tests/golden/evaluate.npz - what the reference's
 own decode_batch, ONNC, Controllability_* and the block run/sample.py:245-273 answered (tools/make_golden_evaluate.py); the fp32
-operation order against float64 and the bound the GPU tests judge the kernel by; include/musehip_eval.h against the compiler and both
-libraries' exports; the driver loops of musediffusion_amd.sampling with an injected sampler and a stub decode.  No kernel runs here:
-the device side is tests/test_evaluate_gpu.py."""
+operation order against float64 and the bound the GPU tests judge the kernel by; the driver loops of musediffusion_amd.sampling with an
+injected sampler and a stub decode.  No kernel runs here: the device side is tests/test_evaluate_gpu.py."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,10 +13,8 @@ import torch
 from conftest import GOLDEN, load_golden
 
 import evaluate_ref as ev
-from musediffusion_amd import _abi, _lib, evaluation, sampling
+from musediffusion_amd import _lib, evaluation, sampling
 from musediffusion_amd.utils import decode_util as du
-from test_abi_cpu import compile_check, translation_unit
-from test_host_cpu import _exports
 
 FIX = {}
 
@@ -143,43 +139,7 @@ def test_selection_rule_and_acceptance_rule():
     assert ev.uncompact([2, 0, 1, 3], [False, True, True]).tolist() == [-1, 4, 1, -1, 2, 5]
 
 
-# ------------------------------------------------------------------------------------------------------------------ the ABI
-def test_eval_header_against_the_compiler(tmp_path):
-    h = _abi.load("musehip.h")
-    d = _abi.load("musehip_eval.h", h)
-    assert list(d.protos) == ["mhe_msim_nearest", "mhe_nearest_key_tile"] and not d.structs and not d.enums
-    assert d.protos["mhe_msim_nearest"] == (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                                      C.c_void_p, C.c_void_p, C.c_void_p])
-    assert d.protos["mhe_nearest_key_tile"] == (C.c_int, [])
-    include = '#include "musehip_eval.h"\n'
-    r = compile_check(include + translation_unit({}, d.protos), tmp_path / "eval_abi.cpp")
-    assert r.returncode == 0, r.stderr[-4000:]
-    wrong = {n: (res, list(args)) for n, (res, args) in d.protos.items()}  # the control: a wrong table fails the same translation unit
-    wrong["mhe_msim_nearest"][1][1] = C.c_int
-    wrong["mhe_nearest_key_tile"][1].append(C.c_int)
-    r = compile_check(include + translation_unit({}, wrong), tmp_path / "eval_abi_wrong.cpp")
-    assert r.returncode != 0 and "mhe_msim_nearest: argument 1" in r.stderr and "mhe_nearest_key_tile: arity" in r.stderr
-    assert "mhe_msim_nearest: argument 0" not in r.stderr
-
-
-def test_both_libraries_export_the_eval_symbols_and_the_other_tables_are_unchanged():
-    assert list(_lib.EVAL_SIGNATURES) == list(_abi.load("musehip_eval.h", _abi.load("musehip.h")).protos) and _lib.EVAL_ENUMS == {}
-    assert len(_lib.SIGNATURES) == 157 and len(_lib.DATA_SIGNATURES) == 4
-    assert not set(_lib.EVAL_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.DBG_SIGNATURES) | set(_lib.DATA_SIGNATURES))
-    for path in (_lib.LIB_PATH, _lib.DBG_LIB_PATH):
-        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        assert {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("mhe_")} == set(_lib.EVAL_SIGNATURES)
-        assert not _exports(path) & set(_lib.EVAL_SIGNATURES)
-    handle = _lib.lib()
-    for name, (res, args) in _lib.EVAL_SIGNATURES.items():
-        fn = getattr(handle, name)
-        assert fn.restype is res and list(fn.argtypes) == args
-    assert handle.mh_abi_version() == 1 and handle.mhe_nearest_key_tile() > 0 and handle.mhe_nearest_key_tile() * 56 * 4 <= 32 << 10
-    with _lib.debug_library() as dbg:
-        assert all(hasattr(dbg, n) for n in _lib.EVAL_SIGNATURES) and dbg.mhe_nearest_key_tile() == handle.mhe_nearest_key_tile()
-    assert _lib.lib() is handle
-
-
+# ------------------------------------------------------------------------------------------------------------- the refusals
 def test_argument_checks_need_no_device():
     """the refusals come before any launch: MH_ERR_INVALID and a text"""
     L = _lib.lib()

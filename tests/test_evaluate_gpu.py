@@ -7,7 +7,6 @@ with the real modify / generate.
 
 Bound (tests/test_evaluate_cpu.py holds the fp32 operation order to half of it): |sim - sim_f64| <= tau (sum |r||r'|)(sum |m||m'|)
 (sum |h||h'|), tau = 58 * 2^-24; an index j is accepted iff sim_f64(i, j) >= (1 - 2 tau) max_j' sim_f64(i, j'), or the NaN rule applies."""
-import ctypes
 import os
 
 import numpy as np
@@ -17,6 +16,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import evaluate_ref as ev  # noqa: E402
+from gpu_helpers import library_launches  # noqa: E402
 from musediffusion_amd import _lib, evaluation, metric, sampling  # noqa: E402
 from musediffusion_amd.utils import decode_util as du  # noqa: E402
 from test_evaluate_cpu import batches, fixture  # noqa: E402
@@ -285,20 +285,6 @@ def test_onnc_sets_against_the_gemm_path_and_with_unequal_halves():
 
 
 # ------------------------------------------------------------------------------------------------ evaluate_batch / MetricTotals
-def library_launches(fn):
-    """the kernels the library launched while fn ran, from its launch recorder"""
-    L = _lib.lib()
-    torch.cuda.synchronize()
-    assert L.mh_profile_start() == 0
-    try:
-        fn()
-    finally:
-        buf = ctypes.create_string_buffer(1 << 16)
-        need = L.mh_profile_stop(buf, len(buf))
-    assert 0 < need <= len(buf)
-    return [ln.split("\t")[0] for ln in buf.value.decode().splitlines() if ln]
-
-
 def test_evaluate_batch_and_totals_reproduce_every_record():
     totals = evaluation.MetricTotals(DEV)
     for n, b in enumerate(batches()):

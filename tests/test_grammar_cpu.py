@@ -1,17 +1,13 @@
-"""Grammar-constrained rounding without a device: the restatement tests/grammar_ref.py against brute-force enumeration of every
-accepted string, constrained rows through the decode restatement (tests/decode_ref.py, strict), every status on hand-made rows,
-include/musehip_grammar.h against the compiler and both libraries' exports, the refusals."""
+"""Grammar-constrained rounding without a device: the restatement tests/grammar_ref.py against brute-force enumeration of every accepted
+string, constrained rows through the decode restatement (tests/decode_ref.py, strict), every status on hand-made rows, the refusals."""
 import ctypes as C
-import subprocess
 
 import numpy as np
 import pytest
 
 import decode_ref as dr
 import grammar_ref as gr
-from musediffusion_amd import _abi, _lib
-from test_abi_cpu import compile_check, translation_unit
-from test_host_cpu import _exports
+from musediffusion_amd import _lib
 
 
 def int_tables(g, n, lo=-64, hi=64):
@@ -208,63 +204,7 @@ def test_class_winners_restatement():
     assert (ci[:, :7] == -1).all() and (ci[:, 7] == 0).all() and np.isneginf(cs).all()
 
 
-# ------------------------------------------------------------------------------------------------------------------ the ABI
-def test_grammar_header_against_the_compiler(tmp_path):
-    h = _abi.load("musehip.h")
-    d = _abi.load("musehip_grammar.h", h)
-    assert list(d.protos) == ["mhg_note_classes", "mhg_class_argmax", "mhg_constrain_workspace_bytes", "mhg_constrain_rows"]
-    assert list(d.structs) == ["mhg_classes"] and C.sizeof(d.structs["mhg_classes"]) == 56
-    assert d.enums == {"MHG_PAD": 0, "MHG_EOS": 1, "MHG_BAR": 2, "MHG_PITCH": 3, "MHG_VELOCITY": 4, "MHG_DURATION": 5, "MHG_POSITION": 6,
-                       "MHG_ANY": 7, "MHG_BARS_EXACT": 0, "MHG_BARS_DECODABLE": 1, "MHG_OK": 0, "MHG_BAD_MASK": 1, "MHG_NO_CHORDS": 2,
-                       "MHG_TOO_MANY_BARS": 3, "MHG_BAD_BOUNDS": 4, "MHG_NO_ROOM": 5, "MHG_NONFINITE": 6}
-    assert [getattr(gr, n) for n in gr.STATUS_NAMES] == [d.enums["MHG_" + n] for n in gr.STATUS_NAMES]
-    assert (gr.PAD, gr.EOS, gr.BAR, gr.PITCH, gr.VELOCITY, gr.DURATION, gr.POSITION, gr.ANY) == tuple(
-        d.enums["MHG_" + n] for n in ("PAD", "EOS", "BAR", "PITCH", "VELOCITY", "DURATION", "POSITION", "ANY"))
-    P, I = C.c_void_p, C.c_int
-    assert d.protos["mhg_note_classes"] == (I, [P])
-    assert d.protos["mhg_class_argmax"] == (I, [P] * 6 + [C.c_int64, I, I, I, P])
-    assert d.protos["mhg_constrain_workspace_bytes"] == (C.c_size_t, [I, I])
-    assert d.protos["mhg_constrain_rows"] == (I, [P] * 6 + [I] + [P] * 5 + [C.c_size_t, I, I, P])
-    include = '#include "musehip_grammar.h"\n'
-    enums = "".join('static_assert(%s == %d, "%s");\n' % (k, v, k) for k, v in d.enums.items())
-    r = compile_check(include + enums + translation_unit(d.structs, d.protos), tmp_path / "grammar_abi.cpp")
-    assert r.returncode == 0, r.stderr[-4000:]
-    wrong = {n: (res, list(args)) for n, (res, args) in d.protos.items()}  # the control: a wrong table fails the same translation unit
-    wrong["mhg_class_argmax"][1][6] = C.c_int                              # n_tokens is an int64
-    r = compile_check(include + translation_unit({}, wrong), tmp_path / "grammar_abi_wrong.cpp")
-    assert r.returncode != 0 and "mhg_class_argmax: argument 6" in r.stderr and "mhg_class_argmax: argument 5" not in r.stderr
-    wrong["mhg_constrain_rows"][1].append(C.c_int)
-    r = compile_check(include + translation_unit({}, wrong), tmp_path / "grammar_abi_arity.cpp")
-    assert r.returncode != 0 and "mhg_constrain_rows: arity" in r.stderr
-    r = compile_check(include + 'static_assert(MHG_NONFINITE == 5, "MHG_NONFINITE");\n', tmp_path / "grammar_enum_wrong.cpp")
-    assert r.returncode != 0 and "MHG_NONFINITE" in r.stderr
-
-
-def test_both_libraries_export_the_grammar_symbols_and_the_other_tables_are_unchanged():
-    assert list(_lib.GRAMMAR_SIGNATURES) == list(_abi.load("musehip_grammar.h", _abi.load("musehip.h")).protos)
-    assert len(_lib.SIGNATURES) == 157 and len(_lib.DATA_SIGNATURES) == 4 and len(_lib.EVAL_SIGNATURES) == 2
-    assert len(_lib.STATS_SIGNATURES) == 2 and len(_lib.INFILL_SIGNATURES) == 2 and len(_lib.HARMONY_SIGNATURES) == 1
-    others = (set(_lib.SIGNATURES) | set(_lib.DBG_SIGNATURES) | set(_lib.DATA_SIGNATURES) | set(_lib.EVAL_SIGNATURES) |
-              set(_lib.STATS_SIGNATURES) | set(_lib.INFILL_SIGNATURES) | set(_lib.HARMONY_SIGNATURES))
-    assert not set(_lib.GRAMMAR_SIGNATURES) & others
-    for path in (_lib.LIB_PATH, _lib.DBG_LIB_PATH):
-        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        names = {ln.split()[-1] for ln in out.splitlines() if ln.split()}
-        assert {n for n in names if n.startswith("mhg_")} == set(_lib.GRAMMAR_SIGNATURES)
-        assert not _exports(path) & set(_lib.GRAMMAR_SIGNATURES)
-        for prefix, table in (("mhh_", _lib.HARMONY_SIGNATURES), ("mhi_", _lib.INFILL_SIGNATURES), ("mhs_", _lib.STATS_SIGNATURES),
-                              ("mhe_", _lib.EVAL_SIGNATURES), ("mhd_", _lib.DATA_SIGNATURES)):
-            assert {n for n in names if n.startswith(prefix)} == set(table)
-    handle = _lib.lib()
-    for name, (res, args) in _lib.GRAMMAR_SIGNATURES.items():
-        fn = getattr(handle, name)
-        assert fn.restype is res and list(fn.argtypes) == args
-    assert handle.mh_abi_version() == 1
-    with _lib.debug_library() as dbg:
-        assert all(hasattr(dbg, n) for n in _lib.GRAMMAR_SIGNATURES)
-    assert _lib.lib() is handle
-
-
+# ------------------------------------------------------------------------------------------------------------- the refusals
 def test_note_classes_need_no_device():
     from musediffusion_amd import ops
     from musediffusion_amd.utils import grammar_util as gu

@@ -14,28 +14,13 @@ pytestmark = pytest.mark.gpu
 import decode_ref as dr  # noqa: E402
 import distance_ref as dref  # noqa: E402
 import grammar_ref as gr  # noqa: E402
+from gpu_helpers import Guarded, library_launches  # noqa: E402
 from musediffusion_amd import _lib, ops  # noqa: E402
 from musediffusion_amd.utils import grammar_util as gu  # noqa: E402
 
 DEV = "cuda"
-GUARD = 64
 SENT_F, SENT_I = 12345.0, -77
 CUSTOM = ((0, 1), (1, 5), (5, 5), (60, 68), (68, 70), (80, 90), (-5, 3))    # V = 70: one empty, one across the 64-column seam, one outside V
-
-
-class Guarded:
-    """a sentinel-filled buffer of `shape` between two guard bands"""
-
-    def __init__(self, dtype, *shape):
-        self.n, self.shape = int(np.prod(shape)), shape
-        self.sent = SENT_F if dtype == torch.float32 else SENT_I
-        self.buf = torch.full((self.n + 2 * GUARD,), self.sent, device=DEV, dtype=dtype)
-        self.ptr = self.buf.data_ptr() + 4 * GUARD
-
-    def get(self):
-        host = self.buf.cpu().numpy()
-        assert (host[:GUARD] == self.sent).all() and (host[GUARD + self.n:] == self.sent).all(), "guard band written"
-        return host[GUARD:GUARD + self.n].reshape(self.shape)
 
 
 def f32(a):
@@ -56,7 +41,7 @@ def classes_struct(classes):
 def run_class_argmax(x, W, aux, classes, mode):
     """-> (cls_score [n, 8], cls_idx [n, 8]) as numpy; x, W, aux are device tensors"""
     n, E, V = x.shape[0], x.shape[1], W.shape[0]
-    cs, ci = Guarded(torch.float32, n, 8), Guarded(torch.int32, n, 8)
+    cs, ci = Guarded(n, 8, dtype=torch.float32, sentinel=SENT_F), Guarded(n, 8)
     d = classes_struct(classes)
     _lib.check(_lib.lib().mhg_class_argmax(x.data_ptr(), W.data_ptr(), aux.data_ptr(), ctypes.byref(d), cs.ptr, ci.ptr, n, E, V, mode,
                                            _lib.current_stream()), "mhg_class_argmax")
@@ -152,7 +137,7 @@ def run_constrain(cs, ci, ids, mask, lo=None, hi=None, policy=gr.BARS_EXACT):
     cid = ci if isinstance(ci, torch.Tensor) else i32(ci)
     idd, md = i32(ids), i32(mask)
     lod, hid = (None, None) if lo is None else (i32(lo), i32(hi))
-    out = dict(tokens=Guarded(torch.int32, B, L), status=Guarded(torch.int32, B), path_score=Guarded(torch.float32, B), counts=Guarded(torch.int32, B, 3))
+    out = dict(tokens=Guarded(B, L), status=Guarded(B), path_score=Guarded(B, dtype=torch.float32, sentinel=SENT_F), counts=Guarded(B, 3))
     _lib.check(_lib.lib().mhg_constrain_rows(csd.data_ptr(), cid.data_ptr(), idd.data_ptr(), md.data_ptr(), None if lod is None else lod.data_ptr(),
                                              None if hid is None else hid.data_ptr(), policy, out["tokens"].ptr, out["status"].ptr,
                                              out["path_score"].ptr, out["counts"].ptr, None, 0, B, L, _lib.current_stream()), "mhg_constrain_rows")
@@ -340,20 +325,6 @@ def test_constrain_rows_on_the_kernels_own_tables_decodes():
 
 
 # ------------------------------------------------------------------------------------------------------------------ the Python front
-def library_launches(fn):
-    """the kernels the library launched while fn ran, from its launch recorder (as tests/test_infill_gpu.py)"""
-    lib = _lib.lib()
-    torch.cuda.synchronize()
-    assert lib.mh_profile_start() == 0
-    try:
-        fn()
-    finally:
-        buf = ctypes.create_string_buffer(1 << 16)
-        need = lib.mh_profile_stop(buf, len(buf))
-    assert 0 < need <= len(buf)
-    return [ln.split("\t")[0].strip("()") for ln in buf.value.decode().splitlines() if ln]
-
-
 @pytest.mark.parametrize("mode", [1, 2])
 def test_constrain_tokens_is_two_launches_whatever_the_batch(mode):
     g = np.random.default_rng(9)
@@ -367,7 +338,7 @@ def test_constrain_tokens_is_two_launches_whatever_the_batch(mode):
         x = f32(g.standard_normal((B, L, E)))
         box = []
         bars = torch.tensor([[1, 4]] * B, device=DEV)
-        seen = library_launches(lambda: box.append(gu.constrain_tokens(model, x, i32(ids).long(), i32(mask).long(), bars)))
+        seen = library_launches(lambda: box.append(gu.constrain_tokens(model, x, i32(ids).long(), i32(mask).long(), bars)), strip="()")
         assert seen == ["class_argmax_kernel<%d>" % mode, "constrain_rows_kernel"], seen
         tokens, res = box[0]
         assert tokens.dtype == torch.int64 and tokens.shape == (B, L) and res.status.shape == (B,) and res.counts.shape == (B, 3)

@@ -12,13 +12,14 @@ pytestmark = pytest.mark.gpu
 
 import decode_ref as dr  # noqa: E402
 import grammar_ref as gr  # noqa: E402
+from gpu_helpers import library_launches  # noqa: E402
 from musediffusion_amd import sampling  # noqa: E402
 from musediffusion_amd.models.diffusion import SpacedDiffusion, get_named_beta_schedule, space_timesteps  # noqa: E402
 from musediffusion_amd.models.network import TransformerNetModel  # noqa: E402
 from musediffusion_amd.utils import decode_util as du, grammar_util as gu  # noqa: E402
 from oracle import denoiser as odn  # noqa: E402
 from oracle import fixtures as fx  # noqa: E402
-from test_grammar_gpu import int_tables, library_launches  # noqa: E402
+from test_grammar_gpu import int_tables  # noqa: E402
 
 DEV = "cuda"
 L, E, STEP, B = 128, 32, 4, 6
@@ -85,7 +86,7 @@ def test_argmax_tokens_constrain_and_modify(setup):
     x = torch.randn(B, L, E, generator=torch.Generator().manual_seed(1)).to(DEV)
     plain = m.argmax_tokens(x)
     tok, res = m.argmax_tokens(x, constrain=(cond["input_ids"], cond["input_mask"]))
-    seen = library_launches(lambda: m.argmax_tokens(x, constrain=(cond["input_ids"], cond["input_mask"])))
+    seen = library_launches(lambda: m.argmax_tokens(x, constrain=(cond["input_ids"], cond["input_mask"])), strip="()")
     assert seen == ["class_argmax_kernel<%d>" % mode, "constrain_rows_kernel"], seen   # instead of the plain argmax, not after it
     t2, r2 = gu.constrain_tokens(m, x, cond["input_ids"], cond["input_mask"], "exact")
     assert torch.equal(tok, t2) and torch.equal(res.status, r2.status) and torch.equal(res.path_score, r2.path_score)
@@ -132,7 +133,7 @@ def test_run_generation_and_run_modification_constrained(setup):
     it = iter(batches)
     seen = library_launches(lambda: logs.__setitem__("plain", sampling.run_generation(
         None, None, meta + chord, batch_size=4, seq_len=L, num_samples=100, out_dir=None, max_batches=2, sampler=lambda cond: next(it)[0],
-        log=logs[False].append, device=DEV)))
+        log=logs[False].append, device=DEV)), strip="()")
     plain = logs.pop("plain")
     assert not hasattr(plain, "constrained") and plain.total_valid_count == 6 and not any("Grammar" in s for s in logs[False])
     assert not [k for k in seen if "class_argmax" in k or "constrain_rows" in k]

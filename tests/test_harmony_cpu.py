@@ -1,11 +1,10 @@
 """CPU: the chord-fit rule without a device.  tests/harmony_ref.py (the plain-Python restatement of csrc/harmony.hip) against music -
 every chord token and every key spelled by note names -, on hand-made rows with answers worked out here, on every record of
 tests/golden/decode.npz (the reference's own recorded notes and markers against the decode restatement's), the bar a note starts in
-against the bar ordinal an infill plan gives its tokens; include/musehip_harmony.h against the compiler and both libraries' exports;
+against the bar ordinal an infill plan gives its tokens;
 the refusals of the entry point, which come before any launch.  No kernel runs here: the device side is tests/test_harmony_gpu.py and
 tests/test_harmony_sampling_gpu.py."""
 import ctypes as C
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,11 +12,9 @@ import pytest
 import decode_ref as dr
 import harmony_ref as hr
 import infill_ref as ir
-from musediffusion_amd import _abi, _lib, metric
+from musediffusion_amd import _lib, metric
 from musediffusion_amd.utils import decode_util as du
-from test_abi_cpu import compile_check, translation_unit
 from test_decode_cpu import fixture_cases
-from test_host_cpu import _exports
 
 CHROMATIC = ("c", "c#", "d", "d#", "e", "f", "f#", "g", "g#", "a", "a#", "b")
 # a quality spelled as the intervals a musician names
@@ -92,7 +89,7 @@ def test_every_key_spells_its_scale_by_name():
 
 def test_status_codes_mirror_the_header():
     assert (hr.OK, hr.MASKED, hr.BAD_META, hr.BAD_COUNTS) == tuple(range(4))
-    assert _lib.HARMONY_ENUMS == {"MHH_OK": 0, "MHH_MASKED": 1, "MHH_BAD_META": 2, "MHH_BAD_COUNTS": 3}
+    assert _lib.ABI["musehip_harmony.h"].enums == {"MHH_OK": 0, "MHH_MASKED": 1, "MHH_BAD_META": 2, "MHH_BAD_COUNTS": 3}
     assert (metric.HARMONY_OK, metric.HARMONY_MASKED, metric.HARMONY_BAD_META, metric.HARMONY_BAD_COUNTS) == tuple(range(4))
     assert len(metric.HARMONY_COUNT_NAMES) == 8
 
@@ -241,54 +238,7 @@ def test_a_note_starts_in_the_bar_an_infill_plan_gives_its_tokens():
     assert shifted == {"branch_fewer_by_one_no_bar", "first_token_is_a_note", "gen_shift_mask_1", "mask_one_long"}
 
 
-# ------------------------------------------------------------------------------------------------------------------ the ABI
-def test_harmony_header_against_the_compiler(tmp_path):
-    h = _abi.load("musehip.h")
-    d = _abi.load("musehip_harmony.h", h)
-    assert list(d.protos) == ["mhh_harmony_counts"] and not d.structs
-    assert d.enums == {"MHH_OK": 0, "MHH_MASKED": 1, "MHH_BAD_META": 2, "MHH_BAD_COUNTS": 3}
-    P, I = C.c_void_p, C.c_int
-    assert d.protos["mhh_harmony_counts"] == (I, [P] * 9 + [I] * 4 + [P])
-    include = '#include "musehip_harmony.h"\n'
-    enums = "".join('static_assert(%s == %d, "%s");\n' % (k, v, k) for k, v in d.enums.items())
-    r = compile_check(include + enums + translation_unit({}, d.protos), tmp_path / "harmony_abi.cpp")
-    assert r.returncode == 0, r.stderr[-4000:]
-    wrong = {n: (res, list(args)) for n, (res, args) in d.protos.items()}  # the control: a wrong table fails the same translation unit
-    wrong["mhh_harmony_counts"][1][9] = C.c_int64                          # B is an int
-    r = compile_check(include + translation_unit({}, wrong), tmp_path / "harmony_abi_wrong.cpp")
-    assert r.returncode != 0 and "mhh_harmony_counts: argument 9" in r.stderr and "mhh_harmony_counts: argument 8" not in r.stderr
-    wrong["mhh_harmony_counts"][1].append(C.c_int)
-    r = compile_check(include + translation_unit({}, wrong), tmp_path / "harmony_abi_arity.cpp")
-    assert r.returncode != 0 and "mhh_harmony_counts: arity" in r.stderr
-    r = compile_check(include + 'static_assert(MHH_BAD_COUNTS == 2, "MHH_BAD_COUNTS");\n', tmp_path / "harmony_enum_wrong.cpp")
-    assert r.returncode != 0 and "MHH_BAD_COUNTS" in r.stderr
-
-
-def test_both_libraries_export_the_harmony_symbol_and_the_other_tables_are_unchanged():
-    assert list(_lib.HARMONY_SIGNATURES) == list(_abi.load("musehip_harmony.h", _abi.load("musehip.h")).protos)
-    assert len(_lib.SIGNATURES) == 157 and len(_lib.DATA_SIGNATURES) == 4 and len(_lib.EVAL_SIGNATURES) == 2
-    assert len(_lib.STATS_SIGNATURES) == 2 and len(_lib.INFILL_SIGNATURES) == 2
-    others = (set(_lib.SIGNATURES) | set(_lib.DBG_SIGNATURES) | set(_lib.DATA_SIGNATURES) | set(_lib.EVAL_SIGNATURES) |
-              set(_lib.STATS_SIGNATURES) | set(_lib.INFILL_SIGNATURES))
-    assert not set(_lib.HARMONY_SIGNATURES) & others
-    for path in (_lib.LIB_PATH, _lib.DBG_LIB_PATH):
-        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        names_ = {ln.split()[-1] for ln in out.splitlines() if ln.split()}
-        assert {n for n in names_ if n.startswith("mhh_")} == set(_lib.HARMONY_SIGNATURES)
-        assert not _exports(path) & set(_lib.HARMONY_SIGNATURES)
-        for prefix, table in (("mhi_", _lib.INFILL_SIGNATURES), ("mhs_", _lib.STATS_SIGNATURES), ("mhe_", _lib.EVAL_SIGNATURES),
-                              ("mhd_", _lib.DATA_SIGNATURES)):
-            assert {n for n in names_ if n.startswith(prefix)} == set(table)
-    handle = _lib.lib()
-    for name, (res, args) in _lib.HARMONY_SIGNATURES.items():
-        fn = getattr(handle, name)
-        assert fn.restype is res and list(fn.argtypes) == args
-    assert handle.mh_abi_version() == 1
-    with _lib.debug_library() as dbg:
-        assert all(hasattr(dbg, n) for n in _lib.HARMONY_SIGNATURES)
-    assert _lib.lib() is handle
-
-
+# ------------------------------------------------------------------------------------------------------------- the refusals
 def test_argument_checks_need_no_device():
     """the refusals come before any launch: MH_ERR_INVALID and a text"""
     lib = _lib.lib()

@@ -4,8 +4,6 @@ counts around the 256-thread pass (0, 1, 63, 64, 65, 255, 256, 257, the capacity
 4096, each sorted (bisection), with one swapped pair and reversed (linear scan); chords on, one tick before and one tick after note
 onsets; all keys and time signatures; hostile pitches, ticks and lengths; every max_bars edge; masks; every status over junk lists;
 1, 2 and 65 rows; repeated bits; one launch; every refusal; 512 generated ComMU-shaped pieces through decode_tokens."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
@@ -14,32 +12,17 @@ pytestmark = pytest.mark.gpu
 
 import decode_ref as dr  # noqa: E402
 import harmony_ref as hr  # noqa: E402
+from gpu_helpers import SENTINEL, Guarded, library_launches, same  # noqa: E402
 from musediffusion_amd import _lib, metric  # noqa: E402
 from musediffusion_amd.utils import decode_util as du  # noqa: E402
 
 DEV = "cuda"
-SENTINEL, GUARD = -77, 64
 I32_MIN, I32_MAX = -2 ** 31, 2 ** 31 - 1
 META = [580, 602, 627, 633, 639, 644, 651, 660, 700, 720, 727]
 
 
 def dev(a):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(DEV)
-
-
-class Guarded:
-    """a sentinel-filled int32 buffer of `shape` between two guard bands"""
-
-    def __init__(self, *shape):
-        self.n = int(np.prod(shape))
-        self.shape = shape
-        self.buf = torch.full((self.n + 2 * GUARD,), SENTINEL, device=DEV, dtype=torch.int32)
-        self.ptr = self.buf.data_ptr() + 4 * GUARD
-
-    def get(self):
-        host = self.buf.cpu().numpy()
-        assert (host[:GUARD] == SENTINEL).all() and (host[GUARD + self.n:] == SENTINEL).all(), "guard band written"
-        return host[GUARD:GUARD + self.n].reshape(self.shape)
 
 
 def run(notes, chords, counts3, meta, valid=None, max_bars=0, hist=True):
@@ -57,11 +40,6 @@ def run(notes, chords, counts3, meta, valid=None, max_bars=0, hist=True):
                                              out["status"].ptr, B, max_notes, max_chords, max_bars, _lib.current_stream()), "mhh_harmony_counts")
     torch.cuda.synchronize()
     return {name: g.get() for name, g in out.items()}
-
-
-def same(got, want, what=""):
-    for name in got:
-        assert np.array_equal(got[name], want[name]), (what, name, np.argwhere(got[name] != want[name])[:5].tolist())
 
 
 def check(notes, chords, counts3, meta, valid=None, max_bars=0, hist=True, what=""):
@@ -258,20 +236,6 @@ def test_batch_sizes_and_the_same_bits_on_a_repeated_call(B):
     valid = (g.random(B) < 0.8).astype(np.int32)
     first = check(*args, valid, max_bars=8)
     same(run(*args, valid, max_bars=8), first, "repeat")
-
-
-def library_launches(fn):
-    """the kernels the library launched while fn ran, from its launch recorder (as tests/test_infill_gpu.py)"""
-    lib = _lib.lib()
-    torch.cuda.synchronize()
-    assert lib.mh_profile_start() == 0
-    try:
-        fn()
-    finally:
-        buf = ctypes.create_string_buffer(1 << 16)
-        need = lib.mh_profile_stop(buf, len(buf))
-    assert 0 < need <= len(buf)
-    return [ln.split("\t")[0] for ln in buf.value.decode().splitlines() if ln]
 
 
 def test_python_front_launches_once_whatever_the_batch():

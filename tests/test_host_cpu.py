@@ -124,19 +124,23 @@ def test_alias_modules_and_factory():
 
 
 def _exports(path):
+    """the dynamic symbols a library defines under the ABI's prefixes: mh_ and one letter more per entry-point family"""
     import subprocess
     out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    return {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("mh_")}
+    return {ln.split()[-1] for ln in out.splitlines() if ln.split() and re.match(r"mh[a-z]?_", ln.split()[-1])}
 
 
 def test_library_exports_every_declared_symbol():
-    """include/musehip.h <-> libmusehip.so, include/musehip_dbg.h <-> libmusehip_dbg.so only.  The production library carries no
-    process-global switch: nothing named mh_*_set_* (A/B variants, timing-only ablations, staggers, diagnostics) is exported by it."""
+    """every header of _lib.HEADERS <-> libmusehip.so, include/musehip_dbg.h <-> libmusehip_dbg.so only: each library exports what its
+    headers declare and nothing else under their prefixes.  The production library carries no process-global switch: nothing named
+    mh_*_set_* (A/B variants, timing-only ablations, staggers, diagnostics) is exported by it."""
     from musediffusion_amd import _lib
-    proto = lambda name: set(re.findall(r"\b(mh_[a-z0-9_]+)\s*\(", open(os.path.join(REPO, "include", name)).read()))
-    declared, dbg_declared = proto("musehip.h"), proto("musehip_dbg.h")
+    code = lambda name: re.sub(r"/\*.*?\*/", " ", open(os.path.join(REPO, "include", name)).read(), flags=re.S)   # prose names functions too
+    proto = lambda name: set(re.findall(r"\b(mh[a-z]?_[a-z0-9_]+)\s*\(", code(name)))
+    declared, dbg_declared = set().union(*(proto(name) for name in _lib.HEADERS)), proto("musehip_dbg.h")
     assert declared and dbg_declared and not (declared & dbg_declared)
-    assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
+    assert proto("musehip.h") == set(_lib.SIGNATURES), proto("musehip.h") ^ set(_lib.SIGNATURES)
+    assert declared == set(_lib.PRODUCT_SIGNATURES), declared ^ set(_lib.PRODUCT_SIGNATURES)
     assert dbg_declared == set(_lib.DBG_SIGNATURES), dbg_declared ^ set(_lib.DBG_SIGNATURES)
     handle = _lib.lib()
     for name in declared:

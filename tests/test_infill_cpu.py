@@ -1,22 +1,18 @@
 """CPU: the infill rules without a device.  tests/infill_ref.py (the plain-Python restatement of csrc/infill.hip) on hand-made rows, one
 per rule and per status; the two properties the feature is for - identity and containment - on every record of tests/golden/decode.npz
-and on generated ComMU-shaped rows, judged by the decode restatement (tests/decode_ref.py); include/musehip_infill.h against the
-compiler and both libraries' exports; the refusals of the two entry points, which come before any launch.  No kernel runs here: the
-device side is tests/test_infill_gpu.py and tests/test_infill_sampling_gpu.py."""
+and on generated ComMU-shaped rows, judged by the decode restatement (tests/decode_ref.py); the refusals of the two entry points, which
+come before any launch.  No kernel runs here: the device side is tests/test_infill_gpu.py and tests/test_infill_sampling_gpu.py."""
 import ctypes as C
-import subprocess
 
 import numpy as np
 import pytest
 
 import decode_ref as dr
 import infill_ref as ir
-from musediffusion_amd import _abi, _lib
+from musediffusion_amd import _lib
 from musediffusion_amd.utils import decode_util as du
 from musediffusion_amd.utils import infill_util as iu
-from test_abi_cpu import compile_check, translation_unit
 from test_decode_cpu import fixture_cases
-from test_host_cpu import _exports
 
 BAR, EOS = ir.BAR, ir.EOS
 Q1, Q2, Q3, Q4 = [432, 131, 3, 304], [440, 140, 60, 310], [500, 150, 70, 320], [559, 194, 130, 431]
@@ -33,7 +29,7 @@ def test_status_codes_and_fields_mirror_the_header():
     assert (ir.OK, ir.NO_EOS, ir.BAD_MASK, ir.BAD_RANGE, ir.OVERFLOW) == tuple(range(5))
     assert (iu.INFILL_OK, iu.INFILL_NO_EOS, iu.INFILL_BAD_MASK, iu.INFILL_BAD_RANGE, iu.INFILL_OVERFLOW) == tuple(range(5))
     assert (iu.OK, iu.NO_EOS, iu.BAD_MASK, iu.BAD_RANGE, iu.OVERFLOW) == tuple(range(5)) and sorted(iu.STATUS_MESSAGE) == list(range(5))
-    assert _lib.INFILL_ENUMS == {"MHI_OK": 0, "MHI_NO_EOS": 1, "MHI_BAD_MASK": 2, "MHI_BAD_RANGE": 3, "MHI_OVERFLOW": 4}
+    assert _lib.ABI["musehip_infill.h"].enums == {"MHI_OK": 0, "MHI_NO_EOS": 1, "MHI_BAD_MASK": 2, "MHI_BAD_RANGE": 3, "MHI_OVERFLOW": 4}
     assert iu.FIELDS == {"position": 1, "velocity": 2, "pitch": 4, "duration": 8, "all": 15}
     assert iu.field_bits("all") == 15 and iu.field_bits("pitch") == 4 and iu.field_bits(("velocity", "duration")) == 10
     assert iu.field_bits(5) == 5 and iu.field_bits(["position", "all"]) == 15
@@ -305,51 +301,7 @@ def test_field_mode_keeps_every_other_field_of_every_note():
     assert checked > 100
 
 
-# ------------------------------------------------------------------------------------------------------------------ the ABI
-def test_infill_header_against_the_compiler(tmp_path):
-    h = _abi.load("musehip.h")
-    d = _abi.load("musehip_infill.h", h)
-    assert list(d.protos) == ["mhi_infill_plan", "mhi_infill_splice"] and not d.structs
-    assert d.enums == {"MHI_OK": 0, "MHI_NO_EOS": 1, "MHI_BAD_MASK": 2, "MHI_BAD_RANGE": 3, "MHI_OVERFLOW": 4}
-    P, I = C.c_void_p, C.c_int
-    assert d.protos["mhi_infill_plan"] == (I, [P, P, P, P, I, I, P, P, P, P, I, I, P])
-    assert d.protos["mhi_infill_splice"] == (I, [P, P, P, P, I, P, P, I, I, P])
-    include = '#include "musehip_infill.h"\n'
-    enums = "".join('static_assert(%s == %d, "%s");\n' % (k, v, k) for k, v in d.enums.items())
-    r = compile_check(include + enums + translation_unit({}, d.protos), tmp_path / "infill_abi.cpp")
-    assert r.returncode == 0, r.stderr[-4000:]
-    wrong = {n: (res, list(args)) for n, (res, args) in d.protos.items()}  # the control: a wrong table fails the same translation unit
-    wrong["mhi_infill_plan"][1][4] = C.c_int64                             # room is an int
-    wrong["mhi_infill_splice"][1].append(C.c_int)
-    r = compile_check(include + translation_unit({}, wrong), tmp_path / "infill_abi_wrong.cpp")
-    assert r.returncode != 0 and "mhi_infill_plan: argument 4" in r.stderr and "mhi_infill_splice: arity" in r.stderr
-    assert "mhi_infill_plan: argument 5" not in r.stderr
-    r = compile_check(include + 'static_assert(MHI_OVERFLOW == 3, "MHI_OVERFLOW");\n', tmp_path / "infill_enum_wrong.cpp")
-    assert r.returncode != 0 and "MHI_OVERFLOW" in r.stderr
-
-
-def test_both_libraries_export_the_infill_symbols_and_the_other_tables_are_unchanged():
-    assert list(_lib.INFILL_SIGNATURES) == list(_abi.load("musehip_infill.h", _abi.load("musehip.h")).protos)
-    assert len(_lib.SIGNATURES) == 157 and len(_lib.DATA_SIGNATURES) == 4 and len(_lib.EVAL_SIGNATURES) == 2 and len(_lib.STATS_SIGNATURES) == 2
-    others = set(_lib.SIGNATURES) | set(_lib.DBG_SIGNATURES) | set(_lib.DATA_SIGNATURES) | set(_lib.EVAL_SIGNATURES) | set(_lib.STATS_SIGNATURES)
-    assert not set(_lib.INFILL_SIGNATURES) & others
-    for path in (_lib.LIB_PATH, _lib.DBG_LIB_PATH):
-        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        names = {ln.split()[-1] for ln in out.splitlines() if ln.split()}
-        assert {n for n in names if n.startswith("mhi_")} == set(_lib.INFILL_SIGNATURES)
-        assert not _exports(path) & set(_lib.INFILL_SIGNATURES)
-        for prefix, table in (("mhs_", _lib.STATS_SIGNATURES), ("mhe_", _lib.EVAL_SIGNATURES), ("mhd_", _lib.DATA_SIGNATURES)):
-            assert {n for n in names if n.startswith(prefix)} == set(table)
-    handle = _lib.lib()
-    for name, (res, args) in _lib.INFILL_SIGNATURES.items():
-        fn = getattr(handle, name)
-        assert fn.restype is res and list(fn.argtypes) == args
-    assert handle.mh_abi_version() == 1
-    with _lib.debug_library() as dbg:
-        assert all(hasattr(dbg, n) for n in _lib.INFILL_SIGNATURES)
-    assert _lib.lib() is handle
-
-
+# ------------------------------------------------------------------------------------------------------------- the refusals
 def test_argument_checks_need_no_device():
     """the refusals come before any launch: MH_ERR_INVALID and a text"""
     lib = _lib.lib()

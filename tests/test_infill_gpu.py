@@ -3,8 +3,6 @@
 4096 (one chunk of 256 threads, one short of it, one over, many) with 1, 2 and 65 rows whose ranges differ; a BAR, the EOS and a quad
 on the seams between threads' chunks and between waves; every status; hostile ranges; room that fits exactly and one slot over; field
 masks on malformed quads; the splice on pads, strays, negatives and half quads with junk in every anchored slot."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
@@ -12,32 +10,17 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import infill_ref as ir  # noqa: E402
+from gpu_helpers import Guarded, library_launches  # noqa: E402
 from musediffusion_amd import _lib  # noqa: E402
 from musediffusion_amd.utils import infill_util as iu  # noqa: E402
 from test_infill_cpu import _hostile_fill  # noqa: E402
 
 DEV = "cuda"
-SENTINEL, GUARD = -77, 64
 BAR, EOS = ir.BAR, ir.EOS
 
 
 def dev(a):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(DEV)
-
-
-class Guarded:
-    """a sentinel-filled int32 buffer of `shape` between two guard bands"""
-
-    def __init__(self, *shape):
-        self.n = int(np.prod(shape))
-        self.shape = shape
-        self.buf = torch.full((self.n + 2 * GUARD,), SENTINEL, device=DEV, dtype=torch.int32)
-        self.ptr = self.buf.data_ptr() + 4 * GUARD
-
-    def get(self):
-        host = self.buf.cpu().numpy()
-        assert (host[:GUARD] == SENTINEL).all() and (host[GUARD + self.n:] == SENTINEL).all(), "guard band written"
-        return host[GUARD:GUARD + self.n].reshape(self.shape)
 
 
 def plan(tokens, pmask, lo, hi, room=0, fields=15):
@@ -339,20 +322,6 @@ def test_splice_fills():
 
 
 # ------------------------------------------------------------------------------------------------------------------ launches
-def library_launches(fn):
-    """the kernels the library launched while fn ran, from its launch recorder (as tests/test_evaluate_gpu.py)"""
-    lib = _lib.lib()
-    torch.cuda.synchronize()
-    assert lib.mh_profile_start() == 0
-    try:
-        fn()
-    finally:
-        buf = ctypes.create_string_buffer(1 << 16)
-        need = lib.mh_profile_stop(buf, len(buf))
-    assert 0 < need <= len(buf)
-    return [ln.split("\t")[0] for ln in buf.value.decode().splitlines() if ln]
-
-
 def test_python_front_repeats_its_bits_and_launches_twice_whatever_the_batch():
     g = np.random.default_rng(3)
     counts = {}

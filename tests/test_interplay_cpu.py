@@ -1,11 +1,10 @@
 """CPU: the interplay rule and the song utilities without a device.  tests/interplay_ref.py (the plain-Python restatement of
 csrc/arrange.hip) on hand-made songs with answers worked out here, on every status, and the identities that hold per song;
 utils.arrange_util.align_shift on host tensors, write_song read back by read_song and by read_midi; evaluation.InterplayTotals.ratios
-on host vectors; include/musehip_arrange.h against the compiler and both libraries' exports; the refusals of the entry point, which
+on host vectors; the refusals of the entry point, which
 come before any launch.  No kernel runs here: the device side is tests/test_interplay_gpu.py and tests/test_arrange_sampling_gpu.py."""
 import ctypes as C
 import math
-import subprocess
 from types import SimpleNamespace
 
 import numpy as np
@@ -13,10 +12,8 @@ import pytest
 import torch
 
 import interplay_ref as ir
-from musediffusion_amd import _abi, _lib, evaluation, metric
+from musediffusion_amd import _lib, evaluation, metric
 from musediffusion_amd.utils import arrange_util as au, decode_util as du
-from test_abi_cpu import compile_check, translation_unit
-from test_host_cpu import _exports
 
 META = [580, 602, 627, 633, 639, 644, 651, 660, 700, 720, 727]   # 100 bpm, c major, 4/4
 
@@ -34,7 +31,7 @@ def song_of(*rows, metas=None, **kw):
 
 def test_names_and_status_codes_mirror_the_header():
     assert (ir.OK, ir.MASKED, ir.BAD_COUNTS, ir.BAD_SHIFT, ir.MIXED) == tuple(range(5))
-    assert _lib.ARRANGE_ENUMS == {"MHA_OK": 0, "MHA_MASKED": 1, "MHA_BAD_COUNTS": 2, "MHA_BAD_SHIFT": 3, "MHA_MIXED": 4}
+    assert _lib.ABI["musehip_arrange.h"].enums == {"MHA_OK": 0, "MHA_MASKED": 1, "MHA_BAD_COUNTS": 2, "MHA_BAD_SHIFT": 3, "MHA_MIXED": 4}
     assert (metric.INTERPLAY_OK, metric.INTERPLAY_MASKED, metric.INTERPLAY_BAD_COUNTS, metric.INTERPLAY_BAD_SHIFT,
             metric.INTERPLAY_MIXED) == tuple(range(5))
     assert len(metric.INTERPLAY_COUNT_NAMES) == 8 and len(metric.INTERPLAY_COLUMN_NAMES) == 9
@@ -274,61 +271,7 @@ def test_ratios_on_host_vectors():
     assert "nan" in evaluation.interplay_block(empty)
 
 
-# ------------------------------------------------------------------------------------------------------------------ the ABI
-def test_arrange_header_against_the_compiler(tmp_path):
-    h = _abi.load("musehip.h")
-    d = _abi.load("musehip_arrange.h", h)
-    assert list(d.protos) == ["mha_interplay_counts", "mha_key_tile"] and not d.structs
-    assert d.enums == {"MHA_OK": 0, "MHA_MASKED": 1, "MHA_BAD_COUNTS": 2, "MHA_BAD_SHIFT": 3, "MHA_MIXED": 4}
-    P, I = C.c_void_p, C.c_int
-    assert d.protos["mha_interplay_counts"] == (I, [P] * 10 + [I] * 2 + [P]) and d.protos["mha_key_tile"] == (I, [])
-    include = '#include "musehip_arrange.h"\n'
-    enums = "".join('static_assert(%s == %d, "%s");\n' % (k, v, k) for k, v in d.enums.items())
-    r = compile_check(include + enums + translation_unit({}, d.protos), tmp_path / "arrange_abi.cpp")
-    assert r.returncode == 0, r.stderr[-4000:]
-    wrong = {n: (res, list(args)) for n, (res, args) in d.protos.items()}  # the control: a wrong table fails the same translation unit
-    wrong["mha_interplay_counts"][1][10] = C.c_int64                       # B is an int
-    r = compile_check(include + translation_unit({}, wrong), tmp_path / "arrange_abi_wrong.cpp")
-    assert r.returncode != 0 and "mha_interplay_counts: argument 10" in r.stderr and "mha_interplay_counts: argument 9" not in r.stderr
-    wrong["mha_interplay_counts"][1].append(C.c_int)
-    r = compile_check(include + translation_unit({}, wrong), tmp_path / "arrange_abi_arity.cpp")
-    assert r.returncode != 0 and "mha_interplay_counts: arity" in r.stderr
-    r = compile_check(include + 'static_assert(MHA_MIXED == 3, "MHA_MIXED");\n', tmp_path / "arrange_enum_wrong.cpp")
-    assert r.returncode != 0 and "MHA_MIXED" in r.stderr
-
-
-def test_both_libraries_export_the_arrange_symbols_and_the_other_tables_are_unchanged():
-    h = _abi.load("musehip.h")
-    assert list(_lib.ARRANGE_SIGNATURES) == list(_abi.load("musehip_arrange.h", h).protos)
-    assert len(_lib.SIGNATURES) == 157 and len(_lib.DATA_SIGNATURES) == 4 and len(_lib.EVAL_SIGNATURES) == 2
-    assert len(_lib.STATS_SIGNATURES) == 2 and len(_lib.INFILL_SIGNATURES) == 2 and len(_lib.HARMONY_SIGNATURES) == 1
-    tables = (("mhh_", _lib.HARMONY_SIGNATURES, "musehip_harmony.h"), ("mhi_", _lib.INFILL_SIGNATURES, "musehip_infill.h"),
-              ("mhs_", _lib.STATS_SIGNATURES, "musehip_stats.h"), ("mhe_", _lib.EVAL_SIGNATURES, "musehip_eval.h"),
-              ("mhd_", _lib.DATA_SIGNATURES, "musehip_data.h"), ("mhg_", _lib.GRAMMAR_SIGNATURES, "musehip_grammar.h"),
-              ("mhr_", _lib.REGION_SIGNATURES, "musehip_region.h"), ("mhv_", _lib.SOLVER_SIGNATURES, "musehip_solver.h"),
-              ("mhm_", _lib.STRUCTURE_SIGNATURES, "musehip_structure.h"))
-    others = set(_lib.SIGNATURES) | set(_lib.DBG_SIGNATURES)
-    for _, table, header in tables:
-        assert list(table) == list(_abi.load(header, h).protos), header
-        others |= set(table)
-    assert not set(_lib.ARRANGE_SIGNATURES) & others
-    for path in (_lib.LIB_PATH, _lib.DBG_LIB_PATH):
-        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        names_ = {ln.split()[-1] for ln in out.splitlines() if ln.split()}
-        assert {n for n in names_ if n.startswith("mha_")} == set(_lib.ARRANGE_SIGNATURES)
-        assert not _exports(path) & set(_lib.ARRANGE_SIGNATURES)
-        for prefix, table, _ in tables:
-            assert {n for n in names_ if n.startswith(prefix)} == set(table), prefix
-    handle = _lib.lib()
-    for name, (res, args) in _lib.ARRANGE_SIGNATURES.items():
-        fn = getattr(handle, name)
-        assert fn.restype is res and list(fn.argtypes) == args
-    assert handle.mh_abi_version() == 1 and handle.mha_key_tile() == 512
-    with _lib.debug_library() as dbg:
-        assert all(hasattr(dbg, n) for n in _lib.ARRANGE_SIGNATURES) and dbg.mha_key_tile() == handle.mha_key_tile()
-    assert _lib.lib() is handle
-
-
+# ------------------------------------------------------------------------------------------------------------- the refusals
 def test_argument_checks_need_no_device():
     """the refusals come before any launch: MH_ERR_INVALID and a text"""
     lib = _lib.lib()

@@ -4,8 +4,6 @@ Note counts around the 256-thread pass, the wave and the LDS tile T = mha_key_ti
 T + 1, 2 T + 1, 600), three rows of 4096 notes; songs of 1, 2, 3, 16 and 17 rows; ids interleaved, negative, extreme, NULL; masks;
 shifts up to 2^29 and one past it; every pitch distance 0..127; skipped notes; shuffled notes and shuffled rows; every status in one
 batch; repeated bits; one launch; every refusal; 512 generated ComMU-shaped pieces through decode_tokens, four to a song."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
@@ -14,11 +12,11 @@ pytestmark = pytest.mark.gpu
 
 import decode_ref as dr  # noqa: E402
 import interplay_ref as ir  # noqa: E402
+from gpu_helpers import SENTINEL, Guarded, library_launches  # noqa: E402
 from musediffusion_amd import _lib, metric  # noqa: E402
 from musediffusion_amd.utils import decode_util as du  # noqa: E402
 
 DEV = "cuda"
-SENTINEL, GUARD = -77, 64
 I32_MIN, I32_MAX = -2 ** 31, 2 ** 31 - 1
 META = [580, 602, 627, 633, 639, 644, 651, 660, 700, 720, 727]
 NAMES = ("counts", "pairs", "ticks", "status")
@@ -26,21 +24,6 @@ NAMES = ("counts", "pairs", "ticks", "status")
 
 def dev(a):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(DEV)
-
-
-class Guarded:
-    """a sentinel-filled buffer of `shape` between two guard bands"""
-
-    def __init__(self, *shape, dtype=torch.int32):
-        self.n = int(np.prod(shape))
-        self.shape = shape
-        self.buf = torch.full((self.n + 2 * GUARD,), SENTINEL, device=DEV, dtype=dtype)
-        self.ptr = self.buf.data_ptr() + self.buf.element_size() * GUARD
-
-    def get(self):
-        host = self.buf.cpu().numpy()
-        assert (host[:GUARD] == SENTINEL).all() and (host[GUARD + self.n:] == SENTINEL).all(), "guard band written"
-        return host[GUARD:GUARD + self.n].reshape(self.shape)
 
 
 def run(notes, counts3, meta, valid=None, song=None, shift=None):
@@ -244,20 +227,6 @@ def test_batch_sizes_and_the_same_bits_on_a_repeated_call(B):
     valid = (g.random(B) < 0.85).astype(np.int32)
     first = check(notes, counts3, meta, valid, song, g.integers(0, 3000, size=B) * 0 + 480)
     same(run(notes, counts3, meta, valid, song, np.full(B, 480)), first, "repeat")
-
-
-def library_launches(fn):
-    """the kernels the library launched while fn ran, from its launch recorder (as tests/test_structure_gpu.py)"""
-    lib = _lib.lib()
-    torch.cuda.synchronize()
-    assert lib.mh_profile_start() == 0
-    try:
-        fn()
-    finally:
-        buf = ctypes.create_string_buffer(1 << 16)
-        need = lib.mh_profile_stop(buf, len(buf))
-    assert 0 < need <= len(buf)
-    return [ln.split("\t")[0] for ln in buf.value.decode().splitlines() if ln]
 
 
 def host(ic):

@@ -1,9 +1,8 @@
-"""CPU: the dataset loader's restatement (tests/loader_ref.py) against every record of tests/golden/loader.npz - what the reference's
-own helper_tokenize / helper_filter / collate_batches, Corruptions.__call__, augment.py and Preprocessor answered
+"""CPU: the dataset loader's restatement (tests/loader_ref.py) against every record of tests/golden/loader.npz - what the reference's own
+helper_tokenize / helper_filter / collate_batches, Corruptions.__call__, augment.py and Preprocessor answered
 (tools/make_golden_loader.py) - bit for bit; the epoch order against torch.utils.data.DataLoader; the host side of
-musediffusion_amd.data.dataset (file names, the missing-file error, the `loop` forms); include/musehip_data.h against the compiler
-and against both libraries' exports.  No kernel runs here: the device side is tests/test_loader_gpu.py."""
-import ctypes as C
+musediffusion_amd.data.dataset (file names, the missing-file error, the `loop` forms).  No kernel runs here: the device side is
+tests/test_loader_gpu.py."""
 import itertools
 import random
 
@@ -15,14 +14,11 @@ from conftest import load_golden
 
 import encode_ref as er
 import loader_ref as lr
-from musediffusion_amd import _abi, _lib
 from musediffusion_amd import data as mdata
 from musediffusion_amd.data import corruption as mcorr
 from musediffusion_amd.data import dataset as mds
 from musediffusion_amd.utils import encode_util as menc
 from oracle import batch as ob
-from test_abi_cpu import compile_check, translation_unit
-from test_host_cpu import _exports
 
 FIX = {}
 
@@ -315,41 +311,3 @@ def test_loop_forms(monkeypatch):
                                  corr_kwargs="dict(p=0.4)", use_bucketing=False, augment=True, **kw)
     assert isinstance(full.corruption, mdata.Corruptions) and full.corruption.corr_max == 2 and full.corruption.corr_kwargs == {"p": 0.4}
     assert isinstance(full.augment, mdata.Augment) and not full.use_bucketing and full.seq_len == 128
-
-
-# ------------------------------------------------------------------------------------------------------------------ the ABI
-def test_data_header_against_the_compiler(tmp_path):
-    h = _abi.load("musehip.h")
-    d = _abi.load("musehip_data.h", h)
-    assert list(d.protos) == ["mhd_gather_offsets", "mhd_gather_rows", "mhd_select_rows", "mhd_augment_rows"] and not d.structs
-    assert d.enums == {"MHD_GATHER_OK": 0, "MHD_GATHER_BAD_INDEX": 1, "MHD_GATHER_OVERFLOW": 2, "MHD_AUGMENT_OK": 0,
-                       "MHD_AUGMENT_NOT_ORIGIN": 1, "MHD_AUGMENT_PITCH_RANGE": 2, "MHD_AUGMENT_BAD_ROW": 3}
-    assert d.protos["mhd_gather_offsets"] == (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                                        C.c_int64, C.c_void_p])
-    include = '#include "musehip_data.h"\n'
-    r = compile_check(include + translation_unit({}, d.protos), tmp_path / "data_abi.cpp")
-    assert r.returncode == 0, r.stderr[-4000:]
-    wrong = {n: (res, list(args)) for n, (res, args) in d.protos.items()}  # the control: a wrong table fails the same translation unit
-    wrong["mhd_gather_rows"][1][2] = C.c_int
-    del wrong["mhd_augment_rows"][1][5]
-    r = compile_check(include + translation_unit({}, wrong), tmp_path / "data_abi_wrong.cpp")
-    assert r.returncode != 0 and "mhd_gather_rows: argument 2" in r.stderr and "mhd_augment_rows: arity" in r.stderr
-    assert "mhd_select_rows" not in r.stderr
-
-
-def test_both_libraries_export_the_data_symbols_and_the_main_table_is_unchanged():
-    assert list(_lib.DATA_SIGNATURES) == list(_abi.load("musehip_data.h", _abi.load("musehip.h")).protos)
-    assert len(_lib.SIGNATURES) == 157 and not [n for n in _lib.SIGNATURES if n.startswith("mhd_")]
-    assert not set(_lib.DATA_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.DBG_SIGNATURES))
-    import subprocess
-    for path in (_lib.LIB_PATH, _lib.DBG_LIB_PATH):
-        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        assert {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("mhd_")} == set(_lib.DATA_SIGNATURES)
-        assert not _exports(path) & set(_lib.DATA_SIGNATURES)
-    handle = _lib.lib()
-    for name, (res, args) in _lib.DATA_SIGNATURES.items():
-        fn = getattr(handle, name)
-        assert fn.restype is res and list(fn.argtypes) == args
-    with _lib.debug_library() as dbg:
-        assert all(hasattr(dbg, n) for n in _lib.DATA_SIGNATURES)
-    assert _lib.lib() is handle

@@ -10,6 +10,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import loader_ref as lr  # noqa: E402
+from gpu_helpers import library_launches  # noqa: E402
 from musediffusion_amd import _lib  # noqa: E402
 from musediffusion_amd import data as mdata  # noqa: E402
 from musediffusion_amd.data import dataset as mds  # noqa: E402
@@ -333,21 +334,6 @@ def test_load_data_music_batches_equal_the_reference_collate(data_dir):
             assert np.array_equal(cor[b, 2:len(r)], lr.augment_row(r, k - 12 if k > 5 else k, 0)[0][2:]), b
         else:
             assert np.array_equal(cor[b, 2:len(r)], r[2:]), b
-
-
-def library_launches(fn):
-    """the kernels the library launched while fn ran, from its launch recorder"""
-    import ctypes
-    L = _lib.lib()
-    torch.cuda.synchronize()
-    assert L.mh_profile_start() == 0
-    try:
-        fn()
-    finally:
-        buf = ctypes.create_string_buffer(1 << 16)
-        need = L.mh_profile_stop(buf, len(buf))
-    assert 0 < need <= len(buf)
-    return [ln.split("\t")[0] for ln in buf.value.decode().splitlines() if ln]
 
 
 def test_launch_count_does_not_depend_on_the_batch_size(data_dir, monkeypatch):

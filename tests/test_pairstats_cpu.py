@@ -1,13 +1,12 @@
 """CPU: the pair statistics of a set without a device.  tests/pairstats_ref.py (the numpy restatement of csrc/pairstats.hip's rules and
 of evaluation.GenerationTotals) on hand-made sets; the float64 accumulation bound the GPU tests judge sum[i] by, against math.fsum; the
-self-similarity check behind the default duplicate threshold; include/musehip_stats.h against the compiler and both libraries' exports;
+self-similarity check behind the default duplicate threshold;
 the refusals of mhs_msim_pair_stats, which come before any launch; sampling.run_generation(get_metric=True) with a stub decode and the
 restatement standing in for the kernels.  No kernel runs here: the device side is tests/test_pairstats_gpu.py and
 tests/test_generation_metrics_gpu.py."""
 import ctypes as C
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,11 +14,9 @@ import torch
 
 import evaluate_ref as ev
 import pairstats_ref as pr
-from musediffusion_amd import _abi, _lib, evaluation, metric, sampling
+from musediffusion_amd import _lib, evaluation, metric, sampling
 from musediffusion_amd.utils import decode_util as du
-from test_abi_cpu import compile_check, translation_unit
 from test_evaluate_cpu import META, StubDecoded, _rows, fixture
-from test_host_cpu import _exports
 
 NAN = np.float32("nan")
 
@@ -151,46 +148,7 @@ def test_identical_pieces_reach_the_default_duplicate_threshold():
     assert (1 - s <= 6 * 2.0 ** -24).all() and (s >= pr.DEFAULT_THRESHOLD).all(), float((1 - s).max()) * 2 ** 24
 
 
-# ------------------------------------------------------------------------------------------------------------------ the ABI
-def test_stats_header_against_the_compiler(tmp_path):
-    h = _abi.load("musehip.h")
-    d = _abi.load("musehip_stats.h", h)
-    assert list(d.protos) == ["mhs_msim_pair_stats", "mhs_pair_key_tile"] and not d.structs and not d.enums
-    P, I = C.c_void_p, C.c_int64
-    assert d.protos["mhs_msim_pair_stats"] == (C.c_int, [P, I, P, I, P, P, P, P, C.c_int, C.c_float, P, P, P, P, P])
-    assert d.protos["mhs_pair_key_tile"] == (C.c_int, [])
-    include = '#include "musehip_stats.h"\n'
-    r = compile_check(include + translation_unit({}, d.protos), tmp_path / "stats_abi.cpp")
-    assert r.returncode == 0, r.stderr[-4000:]
-    wrong = {n: (res, list(args)) for n, (res, args) in d.protos.items()}  # the control: a wrong table fails the same translation unit
-    wrong["mhs_msim_pair_stats"][1][9] = C.c_double                        # the threshold is a float
-    wrong["mhs_pair_key_tile"][1].append(C.c_int)
-    r = compile_check(include + translation_unit({}, wrong), tmp_path / "stats_abi_wrong.cpp")
-    assert r.returncode != 0 and "mhs_msim_pair_stats: argument 9" in r.stderr and "mhs_pair_key_tile: arity" in r.stderr
-    assert "mhs_msim_pair_stats: argument 8" not in r.stderr
-    # a double is legal behind a pointer only
-    with pytest.raises(_abi.AbiError):
-        _abi.parse("int mhs_bad(double threshold);", h)
-
-
-def test_both_libraries_export_the_stats_symbols_and_the_other_tables_are_unchanged():
-    assert list(_lib.STATS_SIGNATURES) == list(_abi.load("musehip_stats.h", _abi.load("musehip.h")).protos)
-    assert len(_lib.SIGNATURES) == 157 and len(_lib.DATA_SIGNATURES) == 4 and len(_lib.EVAL_SIGNATURES) == 2
-    assert not set(_lib.STATS_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.DBG_SIGNATURES) | set(_lib.DATA_SIGNATURES) | set(_lib.EVAL_SIGNATURES))
-    for path in (_lib.LIB_PATH, _lib.DBG_LIB_PATH):
-        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        assert {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("mhs_")} == set(_lib.STATS_SIGNATURES)
-        assert not _exports(path) & set(_lib.STATS_SIGNATURES)
-    handle = _lib.lib()
-    for name, (res, args) in _lib.STATS_SIGNATURES.items():
-        fn = getattr(handle, name)
-        assert fn.restype is res and list(fn.argtypes) == args
-    assert handle.mh_abi_version() == 1 and handle.mhs_pair_key_tile() == handle.mhe_nearest_key_tile()
-    with _lib.debug_library() as dbg:
-        assert all(hasattr(dbg, n) for n in _lib.STATS_SIGNATURES) and dbg.mhs_pair_key_tile() == handle.mhs_pair_key_tile()
-    assert _lib.lib() is handle
-
-
+# ------------------------------------------------------------------------------------------------------------- the refusals
 def test_argument_checks_need_no_device():
     """the refusals come before any launch: MH_ERR_INVALID and a text"""
     L = _lib.lib()

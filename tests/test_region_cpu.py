@@ -1,8 +1,7 @@
 """Region-constrained rounding without a device: the restatement tests/region_ref.py against brute-force enumeration of every accepted
 string of every segment, every status on hand-made rows, the restatement's output through the splice restatement (tests/infill_ref.py:
-nothing but pads is dropped), include/musehip_region.h against the compiler and both libraries' exports, the refusals."""
+nothing but pads is dropped), the refusals."""
 import ctypes as C
-import subprocess
 
 import numpy as np
 import pytest
@@ -10,10 +9,8 @@ import pytest
 import decode_ref as dr
 import infill_ref as ir
 import region_ref as rr
-from musediffusion_amd import _abi, _lib
-from test_abi_cpu import compile_check, translation_unit
+from musediffusion_amd import _lib
 from test_decode_cpu import fixture_cases
-from test_host_cpu import _exports
 
 CLASS_RANGE = {rr.PAD: (0, 1), rr.PITCH: (3, 131), rr.VELOCITY: (131, 195), rr.DURATION: (304, 432), rr.POSITION: (432, 560)}
 
@@ -268,55 +265,7 @@ def test_same_property_on_planned_fixture_rows():
     assert planned > 100 and not_planned > 0
 
 
-# ------------------------------------------------------------------------------------------------------------------ the ABI
-def test_region_header_against_the_compiler(tmp_path):
-    h = _abi.load("musehip.h")
-    d = _abi.load("musehip_region.h", h)
-    assert list(d.protos) == ["mhr_constrain_regions"] and not d.structs
-    assert d.enums == {"MHR_OK": 0, "MHR_NOT_PLANNED": 1, "MHR_BAD_PLAN": 2, "MHR_NONFINITE": 3, "MHR_NO_ROOM": 4}
-    assert [getattr(rr, n) for n in rr.STATUS_NAMES] == [d.enums["MHR_" + n] for n in rr.STATUS_NAMES]
-    grammar = _abi.load("musehip_grammar.h", h).enums                  # the slots are enum mhg_class, which the header includes
-    assert (rr.PAD, rr.EOS, rr.BAR, rr.PITCH, rr.VELOCITY, rr.DURATION, rr.POSITION, rr.ANY) == tuple(
-        grammar["MHG_" + n] for n in ("PAD", "EOS", "BAR", "PITCH", "VELOCITY", "DURATION", "POSITION", "ANY"))
-    P, I = C.c_void_p, C.c_int
-    assert d.protos["mhr_constrain_regions"] == (I, [P] * 5 + [I] + [P] * 4 + [I, I, P])
-    include = '#include "musehip_region.h"\n'
-    enums = "".join('static_assert(%s == %d, "%s");\n' % (k, v, k) for k, v in d.enums.items())
-    enums += 'static_assert(MHG_ANY == 7, "the header brings enum mhg_class with it");\n'
-    r = compile_check(include + enums + translation_unit(d.structs, d.protos), tmp_path / "region_abi.cpp")
-    assert r.returncode == 0, r.stderr[-4000:]
-    wrong = {n: (res, list(args)) for n, (res, args) in d.protos.items()}  # the control: a wrong table fails the same translation unit
-    wrong["mhr_constrain_regions"][1][5] = C.c_int64                       # fields is an int
-    r = compile_check(include + translation_unit({}, wrong), tmp_path / "region_abi_wrong.cpp")
-    assert r.returncode != 0 and "mhr_constrain_regions: argument 5" in r.stderr and "mhr_constrain_regions: argument 4" not in r.stderr
-    wrong["mhr_constrain_regions"][1].append(C.c_int)
-    r = compile_check(include + translation_unit({}, wrong), tmp_path / "region_abi_arity.cpp")
-    assert r.returncode != 0 and "mhr_constrain_regions: arity" in r.stderr
-    r = compile_check(include + 'static_assert(MHR_NO_ROOM == 3, "MHR_NO_ROOM");\n', tmp_path / "region_enum_wrong.cpp")
-    assert r.returncode != 0 and "MHR_NO_ROOM" in r.stderr
-
-
-def test_both_libraries_export_the_region_symbol_and_the_tables_are_disjoint():
-    assert list(_lib.REGION_SIGNATURES) == list(_abi.load("musehip_region.h", _abi.load("musehip.h")).protos)
-    assert _lib.REGION_ENUMS == {"MHR_OK": 0, "MHR_NOT_PLANNED": 1, "MHR_BAD_PLAN": 2, "MHR_NONFINITE": 3, "MHR_NO_ROOM": 4}
-    others = (set(_lib.SIGNATURES) | set(_lib.DBG_SIGNATURES) | set(_lib.DATA_SIGNATURES) | set(_lib.EVAL_SIGNATURES) |
-              set(_lib.STATS_SIGNATURES) | set(_lib.INFILL_SIGNATURES) | set(_lib.HARMONY_SIGNATURES) | set(_lib.GRAMMAR_SIGNATURES))
-    assert not set(_lib.REGION_SIGNATURES) & others
-    for path in (_lib.LIB_PATH, _lib.DBG_LIB_PATH):
-        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        names = {ln.split()[-1] for ln in out.splitlines() if ln.split()}
-        assert {n for n in names if n.startswith("mhr_")} == set(_lib.REGION_SIGNATURES)
-        assert not _exports(path) & set(_lib.REGION_SIGNATURES)
-    handle = _lib.lib()
-    for name, (res, args) in _lib.REGION_SIGNATURES.items():
-        fn = getattr(handle, name)
-        assert fn.restype is res and list(fn.argtypes) == args
-    assert handle.mh_abi_version() == 1
-    with _lib.debug_library() as dbg:
-        assert all(hasattr(dbg, n) for n in _lib.REGION_SIGNATURES)
-    assert _lib.lib() is handle
-
-
+# ------------------------------------------------------------------------------------------------------------- the refusals
 def test_python_mirrors_need_no_device():
     from musediffusion_amd.utils import grammar_util as gu
     assert (gu.REGION_OK, gu.REGION_NOT_PLANNED, gu.REGION_BAD_PLAN, gu.REGION_NONFINITE, gu.REGION_NO_ROOM) == tuple(range(5))

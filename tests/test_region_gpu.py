@@ -12,9 +12,10 @@ pytestmark = pytest.mark.gpu
 
 import infill_ref as ir  # noqa: E402
 import region_ref as rr  # noqa: E402
+from gpu_helpers import Guarded, library_launches  # noqa: E402
 from musediffusion_amd import _lib, ops  # noqa: E402
 from musediffusion_amd.utils import grammar_util as gu  # noqa: E402
-from test_grammar_gpu import Guarded, f32, i32, library_launches  # noqa: E402
+from test_grammar_gpu import SENT_F, f32, i32, same  # noqa: E402
 from test_infill_gpu import plan as device_plan, random_batch, splice as device_splice  # noqa: E402
 from test_region_cpu import CLASS_RANGE  # noqa: E402
 
@@ -28,19 +29,13 @@ def run_regions(cs, ci, ptok, pmask, pstat, fields=15):
     csd = cs if isinstance(cs, torch.Tensor) else f32(cs)
     cid = ci if isinstance(ci, torch.Tensor) else i32(ci)
     t, m, s = i32(ptok), i32(pmask), i32(pstat)
-    out = dict(tokens=Guarded(torch.int32, B, L), status=Guarded(torch.int32, B), path_score=Guarded(torch.float32, B),
-               counts=Guarded(torch.int32, B, 4))
+    out = dict(tokens=Guarded(B, L), status=Guarded(B), path_score=Guarded(B, dtype=torch.float32, sentinel=SENT_F),
+               counts=Guarded(B, 4))
     _lib.check(_lib.lib().mhr_constrain_regions(csd.data_ptr(), cid.data_ptr(), t.data_ptr(), m.data_ptr(), s.data_ptr(), fields,
                                                 out["tokens"].ptr, out["status"].ptr, out["path_score"].ptr, out["counts"].ptr, B, L,
                                                 _lib.current_stream()), "mhr_constrain_regions")
     torch.cuda.synchronize()
     return {k: v.get() for k, v in out.items()}
-
-
-def same(got, want, what=""):
-    for name in ("status", "counts", "tokens"):
-        assert np.array_equal(got[name], want[name]), (what, name, np.argwhere(got[name] != want[name])[:5].tolist(), got["status"][:8], want["status"][:8])
-    assert np.array_equal(got["path_score"].view(np.int32), want["path_score"].view(np.int32)), (what, got["path_score"][:4], want["path_score"][:4])
 
 
 def check(cs, ci, ptok, pmask, pstat=None, fields=15, what=""):
@@ -327,8 +322,8 @@ def test_python_front_is_one_launch_whatever_the_batch(mode):
         x = f32(g.standard_normal((B, L, E)))
         cs, ci = gu.class_tables(model, x)
         box = []
-        assert library_launches(lambda: box.append(gu.constrain_regions(cs, ci, plan))) == ["constrain_regions_kernel"]
-        seen = library_launches(lambda: box.append(gu.constrain_region_tokens(model, x, plan)))
+        assert library_launches(lambda: box.append(gu.constrain_regions(cs, ci, plan)), strip="()") == ["constrain_regions_kernel"]
+        seen = library_launches(lambda: box.append(gu.constrain_region_tokens(model, x, plan)), strip="()")
         assert seen == ["class_argmax_kernel<%d>" % mode, "constrain_regions_kernel"], seen
         (t32, r1), (t64, r2) = box
         assert t32.dtype == torch.int32 and t64.dtype == torch.int64 and t64.shape == (B, L) and torch.equal(t32.long(), t64)

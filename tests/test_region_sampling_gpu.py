@@ -13,13 +13,13 @@ pytestmark = pytest.mark.gpu
 import decode_ref as dr  # noqa: E402
 import infill_ref as ir  # noqa: E402
 import region_ref as rr  # noqa: E402
+from gpu_helpers import library_launches  # noqa: E402
 from musediffusion_amd import sampling  # noqa: E402
 from musediffusion_amd.models.diffusion import SpacedDiffusion, get_named_beta_schedule, space_timesteps  # noqa: E402
 from musediffusion_amd.models.network import TransformerNetModel  # noqa: E402
 from musediffusion_amd.utils import decode_util as du, grammar_util as gu  # noqa: E402
 from oracle import denoiser as odn  # noqa: E402
 from oracle import fixtures as fx  # noqa: E402
-from test_grammar_gpu import library_launches  # noqa: E402
 from test_infill_sampling_gpu import BARS, KINDS, NOT_PLANNED, _bars_of, bars_tensor  # noqa: E402
 
 DEV = "cuda"
@@ -160,7 +160,7 @@ def test_argmax_tokens_with_a_plan_and_the_mutual_exclusion(setup):
     x = torch.randn(B, L, E, generator=torch.Generator().manual_seed(1)).to(DEV)
     plain = m.argmax_tokens(x)
     tok, res = m.argmax_tokens(x, constrain=plan)
-    seen = library_launches(lambda: m.argmax_tokens(x, constrain=plan))
+    seen = library_launches(lambda: m.argmax_tokens(x, constrain=plan), strip="()")
     assert seen == ["class_argmax_kernel<%d>" % mode, "constrain_regions_kernel"], seen   # instead of the plain argmax, not after it
     t2, r2 = gu.constrain_region_tokens(m, x, plan)
     assert torch.equal(tok, t2) and same_result(res, r2) and tok.dtype == torch.int64
@@ -232,7 +232,7 @@ def test_run_infill_with_region_rounding(setup, tmp_path, monkeypatch):
     for name, kw in (("plain", {}), ("argmax", {"rounding": "argmax"}), ("region", {"rounding": "region"})):
         box = []
         runs[name] = library_launches(lambda: box.append(sampling.run_infill(m, diff, loader, bars=(0, 1), step=STEP, room=1, batch_size=B,
-                                                                              get_metric=False, log=lambda s: None, **kw)))
+                                                                              get_metric=False, log=lambda s: None, **kw)), strip="()")
         assert hasattr(box[0], "region") == (name == "region")
     assert calls == [False] * 4 + [True] * 2
     assert runs["plain"] == runs["argmax"] and runs["plain"][:2] == ["infill_plan_kernel", "infill_splice_kernel"]

@@ -1,9 +1,8 @@
 """CPU: the structure rule without a device.  tests/structure_ref.py (the plain-Python restatement of csrc/structure.hip) on hand-made
 rows with answers worked out here, on the slot and bar seams of all four time signatures, on the notes the rule skips and on every
 status; the table route to an entropy against the direct formula under a derived bound; the reference's own recorded notes of
-tests/golden/decode.npz; evaluation.StructureTotals.ratios and structure_gap on host vectors; include/musehip_structure.h against the
-compiler and both libraries' exports; the refusals of the entry point, which come before any launch.  No kernel runs here: the device
-side is tests/test_structure_gpu.py and tests/test_structure_sampling_gpu.py.
+tests/golden/decode.npz; evaluation.StructureTotals.ratios and structure_gap on host vectors; the refusals of the entry point, which
+come before any launch.  No kernel runs here: the device side is tests/test_structure_gpu.py and tests/test_structure_sampling_gpu.py.
 
 The bound of the table route.  H = (T[N] - S) / N with T[k] = fl(k fl(log2 k)).  Each table entry carries two roundings and log2's own
 error (below one ulp), S eleven more additions of non-negative terms, then one subtraction and one division: fewer than 32 roundings
@@ -11,17 +10,14 @@ of quantities that are at most T[N] + S, hence |H - H_exact| <= 32 * 2^-53 * (T[
 rounding (math.fsum of twelve correctly rounded products below 0.54 each)."""
 import ctypes as C
 import math
-import subprocess
 
 import numpy as np
 import pytest
 
 import decode_ref as dr
 import structure_ref as sr
-from musediffusion_amd import _abi, _lib, evaluation, metric
-from test_abi_cpu import compile_check, translation_unit
+from musediffusion_amd import _lib, evaluation, metric
 from test_decode_cpu import fixture_cases
-from test_host_cpu import _exports
 
 META = [580, 602, 627, 633, 639, 644, 651, 660, 700, 720, 727]   # c major, 4/4: 1920 ticks a bar, 16 slots
 TABLE = metric.xlog2x_host(32768)
@@ -66,7 +62,7 @@ def direct(hist):
 
 def test_names_and_status_codes_mirror_the_header():
     assert (sr.OK, sr.MASKED, sr.BAD_META, sr.BAD_COUNTS) == tuple(range(4))
-    assert _lib.STRUCTURE_ENUMS == {"MHM_OK": 0, "MHM_MASKED": 1, "MHM_BAD_META": 2, "MHM_BAD_COUNTS": 3}
+    assert _lib.ABI["musehip_structure.h"].enums == {"MHM_OK": 0, "MHM_MASKED": 1, "MHM_BAD_META": 2, "MHM_BAD_COUNTS": 3}
     assert (metric.STRUCTURE_OK, metric.STRUCTURE_MASKED, metric.STRUCTURE_BAD_META, metric.STRUCTURE_BAD_COUNTS) == tuple(range(4))
     assert len(NAMES) == 16 and len(set(NAMES)) == 16 and len(metric.STRUCTURE_BAR_NAMES) == 16
     assert (metric.STRUCTURE_MAX_NOTES, metric.STRUCTURE_MAX_BARS) == (32768, 512)
@@ -279,60 +275,7 @@ def test_ratios_and_gap_on_host_vectors():
     assert evaluation.structure_report(r, r) == {"generated": r, "reference": r, "gap": evaluation.structure_gap(r, r)}
 
 
-# ------------------------------------------------------------------------------------------------------------------ the ABI
-def test_structure_header_against_the_compiler(tmp_path):
-    h = _abi.load("musehip.h")
-    d = _abi.load("musehip_structure.h", h)
-    assert list(d.protos) == ["mhm_structure_counts"] and not d.structs
-    assert d.enums == {"MHM_OK": 0, "MHM_MASKED": 1, "MHM_BAD_META": 2, "MHM_BAD_COUNTS": 3}
-    P, I = C.c_void_p, C.c_int
-    assert d.protos["mhm_structure_counts"] == (I, [P] * 9 + [I] * 3 + [P])
-    include = '#include "musehip_structure.h"\n'
-    enums = "".join('static_assert(%s == %d, "%s");\n' % (k, v, k) for k, v in d.enums.items())
-    r = compile_check(include + enums + translation_unit({}, d.protos), tmp_path / "structure_abi.cpp")
-    assert r.returncode == 0, r.stderr[-4000:]
-    wrong = {n: (res, list(args)) for n, (res, args) in d.protos.items()}  # the control: a wrong table fails the same translation unit
-    wrong["mhm_structure_counts"][1][9] = C.c_int64                        # B is an int
-    r = compile_check(include + translation_unit({}, wrong), tmp_path / "structure_abi_wrong.cpp")
-    assert r.returncode != 0 and "mhm_structure_counts: argument 9" in r.stderr and "mhm_structure_counts: argument 8" not in r.stderr
-    wrong["mhm_structure_counts"][1].append(C.c_int)
-    r = compile_check(include + translation_unit({}, wrong), tmp_path / "structure_abi_arity.cpp")
-    assert r.returncode != 0 and "mhm_structure_counts: arity" in r.stderr
-    r = compile_check(include + 'static_assert(MHM_BAD_COUNTS == 2, "MHM_BAD_COUNTS");\n', tmp_path / "structure_enum_wrong.cpp")
-    assert r.returncode != 0 and "MHM_BAD_COUNTS" in r.stderr
-
-
-def test_both_libraries_export_the_structure_symbol_and_the_other_tables_are_unchanged():
-    h = _abi.load("musehip.h")
-    assert list(_lib.STRUCTURE_SIGNATURES) == list(_abi.load("musehip_structure.h", h).protos)
-    assert len(_lib.SIGNATURES) == 157 and len(_lib.DATA_SIGNATURES) == 4 and len(_lib.EVAL_SIGNATURES) == 2
-    assert len(_lib.STATS_SIGNATURES) == 2 and len(_lib.INFILL_SIGNATURES) == 2 and len(_lib.HARMONY_SIGNATURES) == 1
-    tables = (("mhh_", _lib.HARMONY_SIGNATURES, "musehip_harmony.h"), ("mhi_", _lib.INFILL_SIGNATURES, "musehip_infill.h"),
-              ("mhs_", _lib.STATS_SIGNATURES, "musehip_stats.h"), ("mhe_", _lib.EVAL_SIGNATURES, "musehip_eval.h"),
-              ("mhd_", _lib.DATA_SIGNATURES, "musehip_data.h"), ("mhg_", _lib.GRAMMAR_SIGNATURES, "musehip_grammar.h"),
-              ("mhr_", _lib.REGION_SIGNATURES, "musehip_region.h"), ("mhv_", _lib.SOLVER_SIGNATURES, "musehip_solver.h"))
-    others = set(_lib.SIGNATURES) | set(_lib.DBG_SIGNATURES)
-    for _, table, header in tables:
-        assert list(table) == list(_abi.load(header, h).protos), header
-        others |= set(table)
-    assert not set(_lib.STRUCTURE_SIGNATURES) & others
-    for path in (_lib.LIB_PATH, _lib.DBG_LIB_PATH):
-        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        names_ = {ln.split()[-1] for ln in out.splitlines() if ln.split()}
-        assert {n for n in names_ if n.startswith("mhm_")} == set(_lib.STRUCTURE_SIGNATURES)
-        assert not _exports(path) & set(_lib.STRUCTURE_SIGNATURES)
-        for prefix, table, _ in tables:
-            assert {n for n in names_ if n.startswith(prefix)} == set(table), prefix
-    handle = _lib.lib()
-    for name, (res, args) in _lib.STRUCTURE_SIGNATURES.items():
-        fn = getattr(handle, name)
-        assert fn.restype is res and list(fn.argtypes) == args
-    assert handle.mh_abi_version() == 1
-    with _lib.debug_library() as dbg:
-        assert all(hasattr(dbg, n) for n in _lib.STRUCTURE_SIGNATURES)
-    assert _lib.lib() is handle
-
-
+# ------------------------------------------------------------------------------------------------------------- the refusals
 def test_argument_checks_need_no_device():
     """the refusals come before any launch: MH_ERR_INVALID and a text"""
     lib = _lib.lib()

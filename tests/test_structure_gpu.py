@@ -4,8 +4,6 @@ sentinel-filled with a guard band on both sides and every element is compared.  
 256, 257, the capacity, 32768); bars_used 1, 3, 4, 5, max_bars - 1 and max_bars at max_bars 1, 4, 64 and 512; slot and bar seams of all
 four time signatures, skipped notes, hostile ticks and pitches; shuffled notes; 1, 2 and 65 rows; masks; every status over junk lists;
 bars NULL and not; repeated bits; one launch; every refusal; 512 generated ComMU-shaped pieces through decode_tokens."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
@@ -14,11 +12,11 @@ pytestmark = pytest.mark.gpu
 
 import decode_ref as dr  # noqa: E402
 import structure_ref as sr  # noqa: E402
+from gpu_helpers import SENTINEL, Guarded, library_launches, same  # noqa: E402
 from musediffusion_amd import _lib, metric  # noqa: E402
 from musediffusion_amd.utils import decode_util as du  # noqa: E402
 
 DEV = "cuda"
-SENTINEL, GUARD = -77, 64
 I32_MIN, I32_MAX = -2 ** 31, 2 ** 31 - 1
 META = [580, 602, 627, 633, 639, 644, 651, 660, 700, 720, 727]
 TABLE = metric.xlog2x_host(32768)            # every call takes a prefix of this one table, the kernel and the restatement alike
@@ -26,21 +24,6 @@ TABLE = metric.xlog2x_host(32768)            # every call takes a prefix of this
 
 def dev(a):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(DEV)
-
-
-class Guarded:
-    """a sentinel-filled buffer of `shape` between two guard bands (int32, or float64 with the sentinel as its value)"""
-
-    def __init__(self, *shape, dtype=torch.int32):
-        self.n = int(np.prod(shape))
-        self.shape = shape
-        self.buf = torch.full((self.n + 2 * GUARD,), SENTINEL, device=DEV, dtype=dtype)
-        self.ptr = self.buf.data_ptr() + self.buf.element_size() * GUARD
-
-    def get(self):
-        host = self.buf.cpu().numpy()
-        assert (host[:GUARD] == SENTINEL).all() and (host[GUARD + self.n:] == SENTINEL).all(), "guard band written"
-        return host[GUARD:GUARD + self.n].reshape(self.shape)
 
 
 def run(notes, counts3, meta, valid=None, max_bars=8, bars=True):
@@ -57,15 +40,6 @@ def run(notes, counts3, meta, valid=None, max_bars=8, bars=True):
                                                B, max_notes, max_bars, _lib.current_stream()), "mhm_structure_counts")
     torch.cuda.synchronize()
     return {name: g.get() for name, g in out.items()}
-
-
-def bits(a):
-    return a.view(np.int64) if a.dtype == np.float64 else a
-
-
-def same(got, want, what=""):
-    for name in got:
-        assert np.array_equal(bits(got[name]), bits(want[name])), (what, name, np.argwhere(bits(got[name]) != bits(want[name]))[:5].tolist())
 
 
 def check(notes, counts3, meta, valid=None, max_bars=8, bars=True, what=""):
@@ -220,20 +194,6 @@ def test_batch_sizes_bars_or_not_and_the_same_bits_on_a_repeated_call(B):
     same(run(*args, valid, max_bars=12), first, "repeat")
     without = check(*args, valid, max_bars=12, bars=False)
     same(without, first, "bars NULL")
-
-
-def library_launches(fn):
-    """the kernels the library launched while fn ran, from its launch recorder (as tests/test_harmony_gpu.py)"""
-    lib = _lib.lib()
-    torch.cuda.synchronize()
-    assert lib.mh_profile_start() == 0
-    try:
-        fn()
-    finally:
-        buf = ctypes.create_string_buffer(1 << 16)
-        need = lib.mh_profile_stop(buf, len(buf))
-    assert 0 < need <= len(buf)
-    return [ln.split("\t")[0] for ln in buf.value.decode().splitlines() if ln]
 
 
 def host(sc):

@@ -7,6 +7,7 @@ no threshold: two launches behind a reverse loop.  profiles/grammar_decode.txt i
     python tools/grammar_bench.py [--config c2] [--calls 50] [--out FILE]"""
 import argparse
 import ctypes
+import functools
 import os
 import statistics
 import sys
@@ -18,30 +19,14 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
 import decode_ref as dr  # noqa: E402  (the tests' generator of ComMU-shaped metas)
+import launch_times  # noqa: E402
 from musediffusion_amd import _lib, ops  # noqa: E402
 from musediffusion_amd.utils import grammar_util as gu  # noqa: E402
 
 SHAPES = {"c2": dict(B=64, L=512, E=128, V=729), "c1": dict(B=8, L=128, E=128, V=729), "ref-default": dict(B=16, L=2096, E=500, V=729)}
 BARS = 8
-
-
-def timed(fn, calls):
-    """kernel name -> [microseconds] of the library launches fn makes, over `calls` calls"""
-    lib = _lib.lib()
-    torch.cuda.synchronize()
-    assert lib.mh_profile_start() == 0
-    try:
-        for _ in range(calls):
-            fn()
-    finally:
-        buf = ctypes.create_string_buffer(1 << 22)
-        need = lib.mh_profile_stop(buf, len(buf))
-    assert 0 < need <= len(buf)
-    out = {}
-    for ln in buf.value.decode().splitlines():
-        f = ln.split("\t")
-        out.setdefault(f[0].strip("()"), []).append(1e3 * float(f[5]))
-    return out
+# the kernels here are template instantiations: named by their whole text, without the launch macro's parentheses (tools/region_bench.py too)
+timed = functools.partial(launch_times.timed, name=lambda kernel: kernel.strip("()"))
 
 
 def main():

@@ -18,39 +18,11 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
 import decode_ref as dr  # noqa: E402  (the tests' generator of ComMU-shaped rows)
+from launch_times import timed  # noqa: E402
 from musediffusion_amd import _lib, metric  # noqa: E402
 from musediffusion_amd.utils import decode_util as du  # noqa: E402
 
 BARS, NOTES_PER_BAR, L = 16, 16, 1280   # 256 notes and one chord per bar: 16 chord changes in a row
-
-
-def timed(fn, calls):
-    """kernel name -> [microseconds] of the library launches fn makes, over `calls` calls"""
-    lib = _lib.lib()
-    torch.cuda.synchronize()
-    assert lib.mh_profile_start() == 0
-    try:
-        for _ in range(calls):
-            fn()
-    finally:
-        buf = ctypes.create_string_buffer(1 << 22)
-        need = lib.mh_profile_stop(buf, len(buf))
-    assert 0 < need <= len(buf)
-    out = {}
-    for ln in buf.value.decode().splitlines():
-        f = ln.split("\t")
-        out.setdefault(f[0].split("(")[0], []).append(1e3 * float(f[5]))
-    return out
-
-
-def make_rows(g, B):
-    rows = []
-    for _ in range(B):
-        meta, chord = dr.make_meta(g, BARS, 0)
-        notes = dr.make_notes(g, BARS, NOTES_PER_BAR)
-        row = meta + chord + [0] + notes
-        rows.append((row + [0] * (L - len(row)), [0] * (len(meta) + len(chord) + 1) + [1] * (L - len(meta) - len(chord) - 1)))
-    return np.array([r[0] for r in rows], np.int32), np.array([r[1] for r in rows], np.int32)
 
 
 def main():
@@ -66,7 +38,7 @@ def main():
              "library launch timer, %d calls after 3 warm-up calls, microseconds per launch: median (min .. max)" % a.calls]
     g = np.random.default_rng(0)
     for B in a.rows:
-        tokens, mask = (torch.from_numpy(x).cuda() for x in make_rows(g, B))
+        tokens, mask = (torch.from_numpy(x).cuda() for x in dr.make_dense_rows(g, B, L, BARS, NOTES_PER_BAR))
         dec = du.decode_tokens(tokens, mask)
         counts = dec.counts.cpu()
         assert not dec.status.any() and int(counts[:, 0].min()) == BARS * NOTES_PER_BAR and int(counts[:, 1].min()) == BARS

@@ -17,29 +17,11 @@ import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
+from launch_times import timed  # noqa: E402
 from musediffusion_amd import _lib, metric  # noqa: E402
 
 META = [580, 602, 627, 633, 639, 644, 651, 660, 700, 720, 727]
 BARS = 16
-
-
-def timed(fn, calls):
-    """kernel name -> [microseconds] of the library launches fn makes, over `calls` calls"""
-    lib = _lib.lib()
-    torch.cuda.synchronize()
-    assert lib.mh_profile_start() == 0
-    try:
-        for _ in range(calls):
-            fn()
-    finally:
-        buf = ctypes.create_string_buffer(1 << 22)
-        need = lib.mh_profile_stop(buf, len(buf))
-    assert 0 < need <= len(buf)
-    out = {}
-    for ln in buf.value.decode().splitlines():
-        f = ln.split("\t")
-        out.setdefault(f[0].split("(")[0], []).append(1e3 * float(f[5]))
-    return out
 
 
 def event_timed(fn, calls):

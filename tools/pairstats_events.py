@@ -28,20 +28,12 @@ def unit_rows(n, seed):
 
 def timed(fn, calls):
     """kernel name -> (detail, [milliseconds]) of the library launches fn makes, over `calls` calls"""
-    L = _lib.lib()
-    torch.cuda.synchronize()
-    assert L.mh_profile_start() == 0
-    try:
+    def run():
         for _ in range(calls):
             fn()
-    finally:
-        buf = ctypes.create_string_buffer(1 << 20)
-        need = L.mh_profile_stop(buf, len(buf))
-    assert 0 < need <= len(buf)
     out = {}
-    for ln in buf.value.decode().splitlines():
-        f = ln.split("\t")
-        out.setdefault(f[0], (f[1], []))[1].append(float(f[5]))
+    for r in _lib.record_launches(run):
+        out.setdefault(r.kernel, (r.detail, []))[1].append(r.ms)
     return out
 
 

@@ -3,7 +3,6 @@
 events (mh_profile_start / mh_profile_stop).  Usage: python tools/train_profile.py [--dropout 0.1] [--steps 2]"""
 import argparse
 import collections
-import ctypes
 import os
 import sys
 
@@ -48,21 +47,19 @@ for _ in range(3):
 e1.record()
 torch.cuda.synchronize()
 print("dropout %.2f: %.2f ms per micro-batch (fwd + bwd, unprofiled)" % (a.dropout, e0.elapsed_time(e1) / 3))
-lib = _lib.lib()
-_lib.check(lib.mh_profile_start())
-for _ in range(a.steps):
-    step()
-buf = ctypes.create_string_buffer(1 << 24)
-need = lib.mh_profile_stop(buf, len(buf))
-assert 0 < need <= len(buf)
+def steps():
+    for _ in range(a.steps):
+        step()
+
+
 acc = collections.defaultdict(lambda: [0, 0.0])
 tot = 0.0
-for line in buf.value.decode().splitlines():
-    kernel, note, grid, block, stream, ms = line.split("\t")
-    key = kernel.strip("()")[:60] + (" | " + " ".join(x for x in note.split() if x.split("=")[0] in ("tile", "epi", "act", "M", "N", "K", "drop", "splits")) if note else "")
+for r in _lib.record_launches(steps):
+    note = r.detail
+    key = r.kernel.strip("()")[:60] + (" | " + " ".join(x for x in note.split() if x.split("=")[0] in ("tile", "epi", "act", "M", "N", "K", "drop", "splits")) if note else "")
     acc[key][0] += 1
-    acc[key][1] += float(ms)
-    tot += float(ms)
+    acc[key][1] += r.ms
+    tot += r.ms
 print("%-110s %6s %9s %6s" % ("kernel | shape", "n/step", "ms/step", "share"))
 for k, (n, ms) in sorted(acc.items(), key=lambda kv: -kv[1][1])[:32]:
     print("%-110s %6.1f %9.3f %5.1f%%" % (k[:110], n / a.steps, ms / a.steps, 100 * ms / tot))
