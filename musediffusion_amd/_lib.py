@@ -1,5 +1,6 @@
 """ctypes binding of libmusehip.so.  The C ABI is the headers under include/ that HEADERS names: musehip.h for the model side and one
-header per entry-point family beside it, each with a prefix of its own (mhd_, mhe_, ...) and exported by both libraries.
+header per entry-point family beside it, each with a prefix of its own (mhd_, mhe_, ...) and exported by both libraries; the
+extension families of EXTENSION_HEADERS (prefixes of two letters: mhac_, ...) are read and bound the same way.
 
 There is no fallback: `lib()` raises if the shared library is absent or does not export the
 symbols the headers declare.  Build it with `python -c "import __graft_entry__ as g; g.build()"`
@@ -42,6 +43,15 @@ def _merged(tables):
 PRODUCT_SIGNATURES = _merged(h.protos for h in ABI.values())
 # every symbol include/musehip.h declares
 SIGNATURES = _H.protos
+# The EXTENSION families: headers of entry points that both libraries export as well, under prefixes of two letters (mhac_, ...), read
+# by the same _abi.load and bound by the same _load.  They stand in a tuple and a table of their own: HEADERS, the number of prototypes
+# per header and PRODUCT_SIGNATURES are pinned by tests/test_abi_cpu.py and tests/test_host_cpu.py, whose export pattern (mh_ and at
+# most one letter more) does not claim a two-letter prefix.  A new family is one more name HERE ("Adding an entry-point
+# family")
+EXTENSION_HEADERS = ("musehip_choose.h",)
+EXTENSION_ABI = {name: _abi.load(name, _H) for name in EXTENSION_HEADERS}
+EXTENSION_SIGNATURES = _merged(h.protos for h in EXTENSION_ABI.values())
+_merged((PRODUCT_SIGNATURES, EXTENSION_SIGNATURES))          # raises on a name that stands in both tables
 # include/musehip_dbg.h: exported by libmusehip_dbg.so only (A/B switches, ablation knobs, diagnostics)
 DBG_SIGNATURES = _abi.load("musehip_dbg.h", _H).protos
 
@@ -87,7 +97,7 @@ def _load(path, signatures, what):
     # runtimes in one process do not share devices, streams or allocations.
     import torch  # noqa: F401
     handle = C.CDLL(path)
-    for name, (res, args) in signatures.items():
+    for name, (res, args) in {**signatures, **EXTENSION_SIGNATURES}.items():   # both libraries export the extension families
         try:
             fn = getattr(handle, name)
         except AttributeError:

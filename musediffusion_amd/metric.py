@@ -23,7 +23,7 @@ Where this module differs from the reference, on purpose (pinned by tests/test_b
 import numpy as np
 import torch
 
-from ._lib import ABI, check, current_stream, lib, ptr, require_device
+from ._lib import ABI, EXTENSION_ABI, check, current_stream, lib, ptr, require_device
 
 
 def get_vectors(tokens, lengths=None, note_len=128, return_status=False):
@@ -439,3 +439,127 @@ def interplay_counts(decoded, song, valid=None, shift=None, pitched_only=True):
     if pitched_only:
         valid = (valid != 0) & (decoded.meta[:, 5] != DRUMS_INST)
     return interplay_counts_raw(decoded.notes, decoded.counts, decoded.meta, valid, song, shift)
+
+
+# ------------------------------------------------------------------- choosing among candidates (csrc/choose.hip), additions
+# mirror of enum mhac_status and enum mhac_limit (include/musehip_choose.h, an extension family: _lib.EXTENSION_HEADERS)
+_CHOOSE = EXTENSION_ABI["musehip_choose.h"].enums
+CHOOSE_OK, CHOOSE_PARTIAL, CHOOSE_EMPTY, CHOOSE_BAD_SCORE = (_CHOOSE["MHAC_" + n] for n in ("OK", "PARTIAL", "EMPTY", "BAD_SCORE"))
+CHOOSE_MAX_TRACKS, CHOOSE_MAX_CANDIDATES, CHOOSE_MAX_COMBINATIONS = (
+    _CHOOSE["MHAC_MAX_" + n] for n in ("TRACKS", "CANDIDATES", "COMBINATIONS"))
+FIT_SCORE_MAX, FIT_WEIGHT_MAX = 1 << 40, 1024
+# Per interval class 0..6 the weight of a common tick: the classes 1, 2 and 6 (seconds and sevenths, the tritone) are what
+# evaluation.InterplayTotals calls dissonant and cost two, thirds, sixths, fourths and fifths earn one, unisons and octaves nothing.
+# A stated convention, not a measured optimum
+DEFAULT_FIT_WEIGHTS = (0, -2, -2, 1, 1, 1, -2)
+
+
+class PairFit:
+    """Device results of mhac_pair_fit on a candidate batch of S songs x T tracks x K candidates (row (s * T + t) * K + k, R = T * K
+    rows a song): status int32 [B] (INTERPLAY_OK ...), ticks and pairs int64 [B, R, 7]: per row, per row of its song (local index
+    t * K + k) and per interval class the common ticks (at most 65535 a pair) and the number of the note pairs that sound together;
+    zeros for the row itself, the rows of its own track, rows out of range and every entry of a row that is not OK."""
+
+    def __init__(self, status, ticks, pairs):
+        self.status, self.ticks, self.pairs = status, ticks, pairs
+
+
+class TrackChoice:
+    """Device results of mhac_choose: choice int32 [S, T] (the kept candidate of every track; -1: a track without an eligible
+    candidate), best and first int64 [S] (the objective of the choice, and of the smallest admissible combination: what one gets
+    without choosing), status int32 [S] (CHOOSE_OK ...).  sampling.arrange adds rows int64 [S * T]: the chosen rows of the candidate
+    batch (candidate 0 for a track that was left out)."""
+
+    def __init__(self, choice, best, first, status):
+        self.choice, self.best, self.first, self.status = choice, best, first, status
+
+
+def _candidate_shape(what, S, T, K):
+    S, T, K = int(S), int(T), int(K)
+    if S < 1 or not 1 <= T <= CHOOSE_MAX_TRACKS or not 1 <= K <= CHOOSE_MAX_CANDIDATES:
+        raise ValueError("%s: S >= 1, T in 1..%d and K in 1..%d (got %d, %d, %d)" % (what, CHOOSE_MAX_TRACKS, CHOOSE_MAX_CANDIDATES, S, T, K))
+    return S, T, K
+
+
+def pair_fit_raw(notes, counts3, meta, S, T, K, valid=None, shift=None):
+    """mhac_pair_fit on the tensors a decode leaves: notes [B, max_notes, 4], counts3 [B, 3], meta [B, 11] with B = S * T * K rows in
+    the candidate layout, valid [B] or None (every row), shift [B] ticks added to a row's notes or None -> PairFit.  The partners of
+    a row are the rows of its song on another track; the rule is the header's.  ONE launch whatever the batch; nothing syncs with
+    the host."""
+    S, T, K = _candidate_shape("pair_fit", S, T, K)
+    B, R = S * T * K, T * K
+    if notes.dim() != 3 or notes.shape[2] != 4 or notes.shape[0] != B:
+        raise ValueError("pair_fit: notes [S * T * K, max_notes, 4]")
+    max_notes = notes.shape[1]
+    if tuple(counts3.shape) != (B, 3) or tuple(meta.shape) != (B, 11):
+        raise ValueError("pair_fit: counts [B, 3] and meta [B, 11]")
+    if shift is not None and tuple(shift.shape) != (B,):
+        raise ValueError("pair_fit: shift holds one entry per row")
+    if not 1 <= max_notes <= INTERPLAY_MAX_NOTES or B * max_notes > 1 << 31:
+        raise ValueError("pair_fit: max_notes in 1..%d and B * max_notes <= 2^31 (got %d, %d)" % (INTERPLAY_MAX_NOTES, max_notes, B))
+    require_device(notes, counts3, meta, valid, shift)
+    dev = notes.device
+    notes, counts3, meta = (t.to(torch.int32).contiguous() for t in (notes, counts3, meta))
+    valid = _mask_i32(valid, B, dev)
+    shift = None if shift is None else shift.to(device=dev, dtype=torch.int32).contiguous()
+    ticks = torch.empty(B, R, 7, device=dev, dtype=torch.int64)
+    pairs = torch.empty(B, R, 7, device=dev, dtype=torch.int64)
+    status = torch.empty(B, device=dev, dtype=torch.int32)
+    check(lib().mhac_pair_fit(ptr(notes), ptr(counts3), ptr(meta), ptr(valid), ptr(shift), ptr(ticks), ptr(pairs), ptr(status), S, T, K,
+                              max_notes, current_stream()), "mhac_pair_fit")
+    return PairFit(status, ticks, pairs)
+
+
+def pair_fit(decoded, S, T, K, shift=None, valid=None):
+    """pair_fit_raw on a DecodedBatch (utils.decode_util.decode_tokens) in the candidate layout; valid defaults to the rows that
+    decoded (decoded.status == OK: the lists of the others hold nothing); shift: ticks per row, as
+    utils.arrange_util.anchor_shift makes them."""
+    if valid is None:
+        valid = decoded.status == 0
+    return pair_fit_raw(decoded.notes, decoded.counts, decoded.meta, S, T, K, valid, shift)
+
+
+def fit_scores(ticks, weights=None):
+    """ticks int64 [S * R, R, 7] (PairFit.ticks), weights: seven integers of magnitude <= 1024, one per interval class (default
+    DEFAULT_FIT_WEIGHTS; a sequence, which is checked, or an int64 tensor, which is clamped to +-1024 where it lives) -> W int64 [S, R, R]: W[s, r, r'] = the sum over the
+    classes of weights[class] * ticks[s * R + r, r', class], clamped to +-2^40.  A few torch operations where the ticks live (host
+    tensors too); a pair of rows has at most 32768^2 pairs of at most 65535 ticks, so the int64 sum is exact."""
+    if ticks.dim() != 3 or ticks.shape[2] != 7 or ticks.shape[1] < 1 or ticks.shape[0] % ticks.shape[1] or ticks.dtype != torch.int64:
+        raise ValueError("fit_scores: ticks int64 [S * R, R, 7]")
+    if isinstance(weights, torch.Tensor):
+        w = weights.to(device=ticks.device, dtype=torch.int64)
+        if tuple(w.shape) != (7,):
+            raise ValueError("fit_scores: seven weights")
+    else:
+        host = [int(x) for x in (DEFAULT_FIT_WEIGHTS if weights is None else weights)]
+        if len(host) != 7 or max(abs(x) for x in host) > FIT_WEIGHT_MAX:
+            raise ValueError("fit_scores: seven integer weights of magnitude <= %d" % FIT_WEIGHT_MAX)
+        w = torch.tensor(host, dtype=torch.int64, device=ticks.device)
+    R = ticks.shape[1]
+    return (ticks * w.clamp(-FIT_WEIGHT_MAX, FIT_WEIGHT_MAX)).sum(2).clamp(-FIT_SCORE_MAX, FIT_SCORE_MAX).view(ticks.shape[0] // R, R, R)
+
+
+def choose_tracks(W, S, T, K, unary=None, eligible=None):
+    """mhac_choose: W int64 [S, R, R] pair scores (fit_scores), unary int64 [S, R] or None (zeros), eligible [S, R] or None (every
+    row) -> TrackChoice: per song the admissible combination of one candidate a track with the largest sum of unary and pair scores,
+    the smallest combination index on a tie.  Exact enumeration: K^T <= 2^20 (the library refuses more).  ONE launch; nothing syncs
+    with the host."""
+    S, T, K = _candidate_shape("choose_tracks", S, T, K)
+    R = T * K
+    if tuple(W.shape) != (S, R, R) or W.dtype != torch.int64:
+        raise ValueError("choose_tracks: W int64 [S, T * K, T * K]")
+    for name, t in (("unary", unary), ("eligible", eligible)):
+        if t is not None and tuple(t.shape) != (S, R):
+            raise ValueError("choose_tracks: %s [S, T * K]" % name)
+    require_device(W, unary, eligible)
+    dev = W.device
+    W = W.contiguous()
+    unary = None if unary is None else unary.to(device=dev, dtype=torch.int64).contiguous()
+    eligible = None if eligible is None else (eligible != 0).to(device=dev, dtype=torch.int32).contiguous()
+    choice = torch.empty(S, T, device=dev, dtype=torch.int32)
+    best = torch.empty(S, device=dev, dtype=torch.int64)
+    first = torch.empty(S, device=dev, dtype=torch.int64)
+    status = torch.empty(S, device=dev, dtype=torch.int32)
+    check(lib().mhac_choose(ptr(W), ptr(unary), ptr(eligible), ptr(choice), ptr(best), ptr(first), ptr(status), S, T, K,
+                            current_stream()), "mhac_choose")
+    return TrackChoice(choice, best, first, status)

@@ -31,7 +31,7 @@ from types import SimpleNamespace
 
 import torch
 
-from . import evaluation, sharding
+from . import evaluation, metric, sharding
 from .models.rounding import denoised_fn_round
 from .utils import arrange_util as au, decode_util as du, grammar_util as gu
 
@@ -216,7 +216,8 @@ class SamplingReport:
     structure=True adds `structure` ({"generated"[, "reference", "gap"]}: evaluation.StructureTotals summaries and their
     evaluation.structure_gap, or None when no batch ran); run_arrangement adds `songs` (the songs written, or that would have been
     without an output directory) and `interplay` (evaluation.InterplayTotals.summary(), or None with interplay=False or when no
-    batch ran) - its total_valid_count counts the tracks that decoded."""
+    batch ran) and `choice` (candidates > 1: the sums of the chosen and the unchosen fit, else None) - its total_valid_count counts
+    the tracks that decoded."""
 
     def __init__(self, total_valid_count, totals, summary, batches):
         self.total_valid_count, self.totals, self.summary, self.batches = total_valid_count, totals, summary, batches
@@ -240,6 +241,12 @@ def _constrained_block(d):
     kept = ", ".join("%s %d" % (k, v) for k, v in rows.items() if k != "ok" and v)
     return ("### Grammar-constrained rounding: %d of %d rows rounded to an accepted sequence (%d Bars, %d notes)%s" % (
         rows["ok"], total, d["bars"], d["notes"], "; left as the plain argmax: " + kept if kept else ""))
+
+
+def _choice_block(c, candidates):
+    """the log block of run_arrangement with candidates > 1"""
+    return ("### Tracks chosen among %d candidates: %d songs, %d with another choice than candidate 0 everywhere\n"
+            "    Fit of the chosen tracks: %d (without choosing: %d)" % (candidates, c["songs"], c["changed"], c["best"], c["first"]))
 
 
 def _structure_report(generated, reference, given, log):
@@ -490,21 +497,50 @@ def run_generation(model, diffusion, midi_meta_dict, *, batch_size, seq_len, num
 
 
 # ------------------------------------------------------------------------------------------------ from single tracks to songs
+def choose_candidates(decoded, S, T, K, weights=None, unary=None):
+    """decoded: the DecodedBatch of a candidate batch (au.candidate_batch: S songs x T tracks x K candidates) -> metric.TrackChoice
+    with `rows` int64 [S * T]: the chosen row of every track of every song.  au.anchor_shift, then two library launches -
+    metric.pair_fit (rows that did not decode and drum rows masked, as evaluation.InterplayTotals masks them: a drum note number is
+    no pitch) and metric.choose_tracks on metric.fit_scores(., weights) with `unary` [S, T * K] int64 or None - and torch operations;
+    nothing syncs with the host.  Eligible is every row that decoded OK, drum rows included: their pair scores are zero.  A track
+    without an eligible candidate keeps candidate 0, whose decode status says that it failed."""
+    ok = decoded.status == du.OK
+    fit = metric.pair_fit(decoded, S, T, K, shift=au.anchor_shift(decoded), valid=ok & (decoded.meta[:, 5] != metric.DRUMS_INST))
+    res = metric.choose_tracks(metric.fit_scores(fit.ticks, weights), S, T, K, unary=unary, eligible=ok.view(S, T * K))
+    res.rows = (torch.arange(S * T, device=ok.device, dtype=torch.int64) * K + res.choice.clamp(min=0).view(-1).long())
+    return res
+
+
 @torch.no_grad()
-def arrange(model, diffusion, base_meta, tracks, n_songs, seq_len, **generate_keywords):
+def arrange(model, diffusion, base_meta, tracks, n_songs, seq_len, candidates=1, weights=None, unary=None, **generate_keywords):
     """`generate` on au.arrangement_batch(base_meta, tracks, n_songs, seq_len), nothing else: every row is one track of one song,
     the rows of a song share the chord progression, tempo, key and time signature of `base_meta` and differ in what `tracks`
     overrides (inst, track_role, pitch_range, min_velocity, max_velocity).  generate_keywords: `generate`'s (step, noise, solver,
-    constrained, ...).  -> (generate's result, song [B], track [B], cond)."""
+    constrained, ...).  -> (generate's result, song [B], track [B], cond).
+    candidates = K > 1: `generate` on au.candidate_batch (every track K times; `noise` is the candidate batch's), ONE decode, and
+    choose_candidates(., weights, unary) keeps of every track the candidate of the best-fitting combination -> (the chosen tokens
+    [n_songs * T, L], song, track and cond of the chosen rows, the metric.TrackChoice with choice, best, first, status and rows).
+    A generate result with a second part (constrained, region) is not carried through the choice: ValueError."""
     device = model.word_embedding.weight.device
-    cond, song, track = au.arrangement_batch(base_meta, tracks, n_songs, seq_len, device)
-    return generate(model, diffusion, cond, **generate_keywords), song, track, cond
+    if int(candidates) == 1:
+        cond, song, track = au.arrangement_batch(base_meta, tracks, n_songs, seq_len, device)
+        return generate(model, diffusion, cond, **generate_keywords), song, track, cond
+    if generate_keywords.get("constrained") or generate_keywords.get("region") is not None:
+        raise ValueError("arrange: candidates > 1 returns the chosen tokens only (no constrained / region result)")
+    T, K = len(tracks), int(candidates)
+    cond, song, track, _ = au.candidate_batch(base_meta, tracks, n_songs, seq_len, K, device)
+    tokens = generate(model, diffusion, cond, **generate_keywords)
+    dec = du.decode_tokens(tokens, cond["input_mask"].to(tokens.device), strict_validation=False)
+    res = choose_candidates(dec, n_songs, T, K, weights, unary)
+    rows = res.rows
+    return (tokens.index_select(0, rows), song.index_select(0, rows.to(song.device)), track.index_select(0, rows.to(track.device)),
+            {k: v.index_select(0, rows.to(v.device)) for k, v in cond.items()}, res)
 
 
 @torch.no_grad()
 def run_arrangement(model, diffusion, base_meta, tracks, *, n_songs, seq_len, num_songs, out_dir, step=None, keep_partial=False,
                     interplay=True, max_batches=None, sampler=None, clip_denoised=True, top_p=1, clamp_step=0, log=print, device="cuda",
-                    solver="ddim", solver_order=2):
+                    solver="ddim", solver_order=2, candidates=1, weights=None):
     """run_generation for songs: ONE au.arrangement_batch of n_songs songs (len(tracks) rows each), sampled again and again until
     num_songs songs are complete (or max_batches batches ran).  Per batch the sampler (`sampler(cond)`, default `generate`, sharded
     when a process group is up), ONE decode without strict validation, au.align_shift (torch operations) and, with `interplay`, one
@@ -514,12 +550,22 @@ def run_arrangement(model, diffusion, base_meta, tracks, *, n_songs, seq_len, nu
     two decoded tracks are written too, from the tracks that decoded, and count.  Rows of a fatal status raise as in run_generation.
     Returns a SamplingReport: total_valid_count = the tracks that decoded, batches, `songs` = the songs that count and `interplay` =
     the summary from one more device -> host copy after the loop, logged as evaluation.interplay_block (None without `interplay` or
-    when no batch ran)."""
+    when no batch ran).
+    candidates = K > 1: the batch is au.candidate_batch (every track K times), decoded once; choose_candidates (two more library
+    launches per batch) keeps one candidate a track and one gather leaves the decoded batch of the chosen rows, on which everything
+    above runs unchanged.  The report gains `choice`: {"best", "first"}: the sums of the chosen and of the unchosen objective over the
+    songs of status OK or PARTIAL, "songs": their number, "changed": those whose choice is not candidate 0 everywhere - from one more
+    device -> host copy after the loop, logged as one block; None at candidates = 1 or when no batch ran."""
     loop = _solver(solver, solver_order)
     if sampler is None:
         sampler = lambda cond: generate(model, diffusion, cond, step, clip_denoised, top_p, clamp_step, sharded=True, **loop)  # noqa: E731
-    cond, song, _ = au.arrangement_batch(base_meta, tracks, n_songs, seq_len, device)
-    T = len(tracks)
+    T, K = len(tracks), int(candidates)
+    if K == 1:
+        cond, song, _ = au.arrangement_batch(base_meta, tracks, n_songs, seq_len, device)
+    else:
+        cond, _, _, _ = au.candidate_batch(base_meta, tracks, n_songs, seq_len, K, device)
+        song = torch.arange(n_songs, device=device, dtype=torch.int32).repeat_interleave(T)
+    chosen = None                                                         # int64 [4] on the device: best, first, songs, changed
     write = out_dir is not None and sharding.rank() == 0
     if write:
         os.makedirs(out_dir, exist_ok=True)
@@ -527,6 +573,15 @@ def run_arrangement(model, diffusion, base_meta, tracks, *, n_songs, seq_len, nu
     while songs < num_songs and (max_batches is None or batch_index < max_batches):
         tokens = sampler(cond)
         dec = du.decode_tokens(tokens, cond["input_mask"].to(tokens.device), strict_validation=False)
+        if K > 1:
+            res = choose_candidates(dec, n_songs, T, K, weights)
+            dec = dec.select(res.rows)
+            counted = (res.status == metric.CHOOSE_OK) | (res.status == metric.CHOOSE_PARTIAL)
+            moved = counted & (res.choice > 0).any(1)
+            zero = torch.zeros_like(res.best)
+            now = torch.stack([torch.where(counted, res.best, zero).sum(), torch.where(counted, res.first, zero).sum(),
+                               counted.sum(), moved.sum()])
+            chosen = now if chosen is None else chosen + now
         shift = au.align_shift(dec, song.to(tokens.device))
         if interplay:
             fit = (fit or evaluation.InterplayTotals(tokens.device)).update(dec, song, shift=shift)
@@ -550,4 +605,8 @@ def run_arrangement(model, diffusion, base_meta, tracks, *, n_songs, seq_len, nu
     report.interplay = fit.summary() if fit is not None else None
     if fit is not None:
         log(evaluation.interplay_block(report.interplay))
+    report.choice = None
+    if chosen is not None:
+        report.choice = dict(zip(("best", "first", "songs", "changed"), chosen.cpu().tolist()))
+        log(_choice_block(report.choice, K))
     return report

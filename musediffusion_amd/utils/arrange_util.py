@@ -44,6 +44,45 @@ def arrangement_batch(base_meta, tracks, n_songs, seq_len, device="cuda"):
     return cond, song, track
 
 
+def candidate_batch(base_meta, tracks, n_songs, seq_len, candidates, device="cuda"):
+    """arrangement_batch with every track of every song `candidates` times: (cond, song, track, cand) with the rows in the candidate
+    layout of include/musehip_choose.h - row (s * T + t) * K + k is candidate k of track t of song s, T = len(tracks), K =
+    candidates; song, track and cand int32 [n_songs * T * K].  The K candidates of a track start from the same row and differ in
+    what the sampler draws.  One meta_to_batch per track and a row gather."""
+    K = int(candidates)
+    if not tracks or n_songs < 1 or K < 1:
+        raise ValueError("candidate_batch: at least one track, one song and one candidate")
+    for t in tracks:
+        unknown = sorted(set(t) - set(TRACK_OVERRIDES))
+        if unknown:
+            raise ValueError("candidate_batch: a track overrides %s, not %s" % (", ".join(TRACK_OVERRIDES), ", ".join(unknown)))
+    T = len(tracks)
+    per_track = [du.meta_to_batch({**base_meta, **t}, n_songs * K, seq_len, device) for t in tracks]
+    row = torch.arange(n_songs * T * K, device=device, dtype=torch.int64)
+    song, track, cand = row // (T * K), row // K % T, row % K
+    rows = track * (n_songs * K) + song * K + cand                       # of the tracks' batches laid end to end
+    cond = {k: torch.cat([c[k] for c in per_track]).index_select(0, rows) for k in ("input_ids", "input_mask")}
+    return cond, song.to(torch.int32), track.to(torch.int32), cand.to(torch.int32)
+
+
+def _bar_ticks(meta):
+    """the ticks of one bar per row by its time-signature token meta[2]: 1920, 1440, 1440 or 2880; 0 for any other token"""
+    ts = meta[:, 2]
+    beats = torch.where(ts == 627, 4, torch.where(ts == 630, 6, torch.where((ts == 628) | (ts == 629), 3, 0)))
+    return beats * du.TICKS_PER_BEAT
+
+
+def anchor_shift(decoded):
+    """decoded: a DecodedBatch -> int32 [B] ticks: one bar for a row that decoded OK and whose first kept token is its first BAR
+    (du.first_bar_shift == 0), else 0.  align_shift moves such a row only when a row of its song has notes in front of its first
+    BAR, so a row's shift depends on the other rows; this one is absolute - every first BAR lands on the tick of bar 1 - so the
+    overlap of two candidate rows does not depend on which other candidates are chosen.  On the rows of a song that decoded it
+    differs from align_shift by one constant (0 or one bar).  Torch operations only, no sync with the host."""
+    f = du.first_bar_shift(decoded)
+    bar = _bar_ticks(decoded.meta)
+    return torch.where((f == 0) & (decoded.status == du.OK), bar, torch.zeros_like(bar)).to(torch.int32)
+
+
 def align_shift(decoded, song):
     """decoded: a DecodedBatch; song [B]: the song of every row -> int32 [B] ticks to add to a row's notes so that the first BAR of
     every track of a song lands on one tick.  f = du.first_bar_shift: a row with f == 1 has notes in front of its first BAR, which

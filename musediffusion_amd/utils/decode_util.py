@@ -119,6 +119,14 @@ class DecodedBatch:
         self.status, self.counts, self.meta = packed[o[0]:o[1]], packed[o[1]:o[2]].view(B, 3), packed[o[2]:o[3]].view(B, 11)
         self.notes, self.chords = packed[o[3]:o[4]].view(B, max_notes, 4), packed[o[4]:o[5]].view(B, max_chords, 2)
 
+    def select(self, rows):
+        """rows: int64 [n] row indices on the device -> the DecodedBatch of those rows, in that order (one gather per field, no sync
+        with the host)"""
+        _, max_notes, max_chords = self._shape
+        packed = torch.cat([t.index_select(0, rows).reshape(-1) for t in (self.status, self.counts, self.meta, self.notes, self.chords)])
+        return DecodedBatch(self.restored.index_select(0, rows), self.lengths.index_select(0, rows), packed, rows.shape[0], max_notes,
+                            max_chords)
+
     def cpu(self):
         """one device -> host copy of everything but the restored rows"""
         B, max_notes, max_chords = self._shape
